@@ -296,7 +296,15 @@ class _Reader:
         cls = dt[0] & 0x0F
         if cls == 3:
             size = struct.unpack_from("<I", dt, 4)[0]
-            return name, body[pos:pos + size].rstrip(b"\0").decode()
+            raw = body[pos:pos + size]
+            if dt[1] & 0x0F == 0:
+                # null-terminated (what save() and Caffe's H5LT helpers
+                # write): the size counts exactly one terminator, so a
+                # value that itself ends in NULs survives the round-trip
+                raw = raw[:-1] if raw.endswith(b"\0") else raw
+            else:
+                raw = raw.rstrip(b"\0")     # null-padded fixed width
+            return name, raw.decode()
         if cls == 1:
             return name, struct.unpack_from("<d", body, pos)[0]
         return name, struct.unpack_from("<q", body, pos)[0]

@@ -30,6 +30,37 @@ def test_bench_json_contract():
     assert {"model", "global_batch", "parallelism"} <= set(d["config"])
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the last timed step's loss, net outputs, weights
+    and gradients land as float .npy files within the 64 MB budget, and
+    --full is accepted alongside."""
+    import numpy as np
+    out_dir = tmp_path / "dump"
+    out = subprocess.run(
+        [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+         "--steps", "2", "--warmup", "1", "--batch", "8",
+         "--model", "cifar10_quick", "--full",
+         "--dump-outputs", str(out_dir)],
+        capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-500:]
+    d = json.loads(out.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    arrays = {p.stem: np.load(p) for p in out_dir.glob("*.npy")}
+    assert {"loss", "out_loss", "weights", "grads"} <= set(arrays)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        assert np.isfinite(a).all(), name
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 2 ** 20
+    # cifar10_quick: 145578 learnable parameters, dumped whole
+    assert arrays["weights"].shape == arrays["grads"].shape == (145578,)
+    assert np.abs(arrays["grads"]).max() > 0
+    # the loss top and the returned weighted loss are the same number
+    assert arrays["loss"].shape == (1,)
+    assert float(arrays["loss"][0]) == float(arrays["out_loss"])
+    # 10-class softmax loss a few steps from init: near ln(10)
+    assert 1.0 < float(arrays["loss"][0]) < 4.0
+
+
 def test_bench_default_args_fast():
     """Driver runs bench.py with no flags: must default to N=1 and finish
     quickly. We only check arg parsing + default batch resolution here."""

@@ -3,8 +3,9 @@ config shipped in yahoo/CaffeOnSpark's data/ must parse with our
 clean-room text codec, survive a binary round-trip, and (for the net
 definitions) build a Net whose layer count matches the file.
 
-The corpus is read from the read-only reference mount when present
-(nothing is copied into this repo); skipped elsewhere."""
+The corpus (configs, the COCO caption sample and the four test jpgs)
+is stored under tests/golden/reference/, one folder per upstream
+resource directory."""
 
 import glob
 import os
@@ -18,19 +19,42 @@ REF_DIRS = [REF,
             "/root/reference/caffe-grid/src/test/resources",
             "/root/reference/caffe-distri/src/test/resources"]
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF),
-                                reason="reference mount not present")
+# The names above are where the corpus was first read from.  They are kept
+# only as the case ids of the parametrized tests, so results stay comparable
+# with earlier runs; the files themselves are the stored copies below.
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                      "golden", "reference")
+STORED = dict(zip(REF_DIRS, (os.path.join(GOLDEN, "data"),
+                             os.path.join(GOLDEN, "caffe-grid"),
+                             os.path.join(GOLDEN, "caffe-distri"))))
+GRID_RES = STORED[REF_DIRS[1]]
+DISTRI_RES = STORED[REF_DIRS[2]]
 
 
 def _files(pattern):
+    """Case ids (original location + file name) of the stored files."""
     out = []
     for d in REF_DIRS:
-        out += glob.glob(os.path.join(d, pattern))
+        out += [os.path.join(d, os.path.basename(p))
+                for p in glob.glob(os.path.join(STORED[d], pattern))]
     return sorted(out)
+
+
+def _stored(case_id):
+    return os.path.join(STORED[os.path.dirname(case_id)],
+                        os.path.basename(case_id))
+
+
+def test_corpus_present():
+    """The parametrized cases below are generated from the stored corpus:
+    an incomplete checkout must fail here, not collect zero cases."""
+    assert len(_files("*solver*.prototxt")) == 10
+    assert len(_files("*.prototxt")) == 23
 
 
 @pytest.mark.parametrize("path", _files("*solver*.prototxt"))
 def test_reference_solver_parses(path):
+    path = _stored(path)
     sp = text_format.parse_file(path, caffe_pb.SolverParameter)
     assert sp.base_lr > 0 or sp.has_field("net") or sp.has_field("train_net")
     # wire round-trip preserves the message
@@ -44,6 +68,7 @@ def test_reference_solver_parses(path):
 @pytest.mark.parametrize("path", [p for p in _files("*.prototxt")
                                   if "solver" not in p])
 def test_reference_net_parses_and_builds(path):
+    path = _stored(path)
     np_ = text_format.parse_file(path, caffe_pb.NetParameter)
     assert len(np_.layer) > 0
     back = caffe_pb.NetParameter.FromString(np_.SerializeToString())
@@ -58,7 +83,7 @@ def test_reference_net_parses_and_builds(path):
     # factored/2-layer variant selection)
     base = os.path.basename(path)
     for sf in _files("*solver*.prototxt"):
-        sp = text_format.parse_file(sf, caffe_pb.SolverParameter)
+        sp = text_format.parse_file(_stored(sf), caffe_pb.SolverParameter)
         if sp.net and os.path.basename(sp.net) == base and \
                 sp.has_field("train_state"):
             state._merge(sp.train_state)
@@ -89,8 +114,7 @@ def test_reference_caffenet_trains_cpu():
     import torch
 
     from caffeonspark_amd.core.solver import Solver
-    sf = os.path.join("/root/reference/caffe-distri/src/test/resources",
-                      "caffenet_solver.prototxt")
+    sf = os.path.join(DISTRI_RES, "caffenet_solver.prototxt")
     sp = text_format.parse_file(sf, caffe_pb.SolverParameter)
     sp.display = 0
     s = Solver(sp, proto_dir=os.path.dirname(sf))
@@ -109,7 +133,7 @@ def test_reference_coco_fixture_pipeline(tmp_path):
     """Run the COCO converter + vocab + embedding pipeline on the
     reference's OWN coco fixtures (ToolTest.scala:36-135 analog)."""
     pytest.importorskip("pandas")
-    res = "/root/reference/caffe-grid/src/test/resources"
+    res = GRID_RES
     if not os.path.exists(os.path.join(res, "coco.json")):
         pytest.skip("fixture missing")
     from caffeonspark_amd.tools.coco import coco_to_dataframe, \
@@ -139,7 +163,7 @@ def test_reference_images_seqfile_train(tmp_path):
     """SourceTest.scala analog on the reference's own 4 jpgs: build a
     SequenceFile with Binary2Sequence, feed it through SeqImageSource
     into the reference's caffenet test net, and step the solver."""
-    imgs = "/root/reference/data/images"
+    imgs = os.path.join(STORED[REF], "images")
     if not os.path.exists(os.path.join(imgs, "labels.txt")):
         pytest.skip("fixture missing")
     try:
@@ -156,7 +180,7 @@ def test_reference_images_seqfile_train(tmp_path):
 
     # caffenet test net reads a MemoryData source_class SeqImage source;
     # clone the reference solver/net with our source wiring
-    res = "/root/reference/caffe-distri/src/test/resources"
+    res = DISTRI_RES
     npar = text_format.parse(
         open(os.path.join(res, "caffenet_train_net.prototxt")).read(),
         caffe_pb.NetParameter)

@@ -28,6 +28,18 @@ def test_hdf5_roundtrip_nested(tmp_path):
                                g["layer.with.dots"]["0"])
 
 
+def test_hdf5_string_attr_keeps_trailing_nul(tmp_path):
+    """A string attribute is stored with exactly one terminator, so values
+    that are empty or end in NUL themselves read back unchanged (the case
+    the hdf5 fuzz test only hits on some draws)."""
+    for i, val in enumerate(["", "\x00", "a\x00\x00", "abc.h5"]):
+        root = hdf5.H5Group()
+        root.attrs["note"] = val
+        f = str(tmp_path / f"s{i}.h5")
+        hdf5.save(f, root)
+        assert hdf5.load(f).attrs["note"] == val
+
+
 def test_hdf5_solver_snapshot_restore(tmp_path):
     """cifar10_quick-style HDF5 snapshot (snapshot_format: HDF5) round-trip
     through the Solver."""

@@ -8,18 +8,41 @@
 // (same for B with N rows).  All four combinations are used by the layer
 // catalog (fc fwd = NT-direct/direct, fc dx = direct/trans, dw = trans/trans).
 //
-// Structure: 128x128 tile, BK=32, 4 waves (2x2), 16x16x32 bf16 MFMA with
-// fp32 accumulation; interior aligned tiles stage A/B via
-// __builtin_amdgcn_global_load_lds (16 B/lane direct-to-LDS DMA); edge or
-// unaligned tiles take a guarded staging path.  XCD-aware block swizzle for
-// L2 locality; optional split-K with fp32 atomic reduction (STORE_MODE 2)
-// for the skinny dw GEMMs.  Epilogue fuses per-column bias add + ReLU.
+// Every kernel works on BK=32 K-tiles held in LDS in ONE canonical layout
+// ([row][32] bf16, 16-byte chunks XOR-swizzled by swz_chunk) and is
+// assembled from the same pieces:
+//   decode_tile      blockIdx -> XCD-swizzled (bm, bn, tile_m, tile_n)
+//   stage_*          global -> LDS; the only part that differs per operand
+//   load_frags_mfma  LDS -> fragments -> 16x16x32 bf16 MFMA (fp32 acc)
+//   pipelined_loop   counted-vmcnt K loop for the DMA-staged kernels
+//   epilogue_bf16    bias + ReLU + alpha, bf16 store or RMW accumulate
+//   epilogue_f32     fp32 plain store or atomic add (split-K)
+//
+// Kernels, their staging policies, and who launches them:
+//   gemm_kernel<TA, TB, STORE_MODE, WAVES>       gemm_bf16[_batched]
+//     128x128 tile; interior aligned NN tiles run pipelined_loop<WAVES, 2>
+//     with ADirect (direct-to-LDS DMA), everything else a guarded loop.
+//     All 16 TAxTBxSTORE_MODE combinations at WAVES=4, NN also at WAVES=8.
+//   gemm_conv_fwd_kernel<WAVES, DEPTH>           gemm_conv_fwd
+//     pipelined_loop<WAVES, DEPTH> with AImplicit (im2col gather DMA).
+//     <8,4> (one barrier per tile) when w8 and 4*BK <= K <= COS_CONVQ,
+//     else <8,2> when w8, else <4,2>.
+//   gemm_conv_fwd_sc_kernel<WAVES>               gemm_conv_fwd_sc
+//     small-C gather through registers, own __syncthreads loop; <8>/<4>.
+//   gemm_wide_tt_kernel<STORE, BStage>           launch_wide_tt
+//     128x256 tile, 8 waves, trans/trans weight gradients with optional
+//     fused db.  BStage = BGuarded (TT branch of gemm_bf16_batched),
+//     BImplicit (gemm_conv_dw), BImplicitSC (gemm_conv_dw_sc); each with
+//     STORE 1 (single split, plain store) or 2 (split-K atomics).
+// w8 (use_w8): 8-wave blocks when M or N <= 256, forced by COS_GEMM_W8.
 //
 // Replaces the reference's cuBLAS calls inside conv/ip layers (SURVEY.md
 // §3.6 rows "Convolution fwd/bwd", "InnerProduct") with a hand-written
 // CDNA4 kernel per the rebuild's north star.
 
 #include "common.h"
+
+#include <type_traits>
 
 namespace cosamd {
 
@@ -40,6 +63,129 @@ constexpr int NTHREADS = 256;
 // (cdna_hip_programming.md §5: swizzle must be both-sides-or-neither).
 __device__ __forceinline__ int swz_chunk(int row, int chunk) {
   return chunk ^ ((row >> 1) & 3);
+}
+
+// ---------------------------------------------------------- shared pieces
+
+struct Tile { int bm, bn, tile_m, tile_n; };
+
+// XCD-aware block swizzle -> output tile of a BM x TBN tiling
+template <int TBN>
+__device__ __forceinline__ Tile decode_tile(int M, int N) {
+  int mblocks = (M + BM - 1) / BM;
+  int nblocks = (N + TBN - 1) / TBN;
+  int bid = xcd_swizzle(blockIdx.x, mblocks * nblocks);
+  Tile t;
+  t.bm = bid / nblocks;
+  t.bn = bid % nblocks;
+  t.tile_m = t.bm * BM;
+  t.tile_n = t.bn * TBN;
+  return t;
+}
+
+// rows / 16-row m-fragments per wave of the 128x128 kernels:
+// WAVES=4: 2x2 wave grid of 64x64; WAVES=8: 4x2 grid of 32x64
+constexpr int mrows_of(int waves) { return BM / (waves / 2); }
+constexpr int mfrags_of(int waves) { return mrows_of(waves) / 16; }
+
+// One K-tile of compute for a wave: MF x 4 fragments (wave tile
+// MROWS x 64 at (wm, wn)) from the canonical swizzled LDS layout, then
+// the MF x 4 MFMA block.  PRIO brackets the MFMAs with s_setprio for the
+// pipelined loops, where other waves are issuing DMA at the same time.
+template <int MF, int MROWS, bool PRIO>
+__device__ __forceinline__ void load_frags_mfma(
+    const bf16* As, const bf16* Bs, int wm, int wn, int lane,
+    f32x4 (&acc)[MF][4]) {
+  int lrow = lane & 15, lchunk = lane >> 4;
+  bf16x8 afrag[MF], bfrag[4];
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    int rb = wn * 64 + f * 16 + lrow;
+    bfrag[f] = *reinterpret_cast<const bf16x8*>(
+        Bs + rb * BK + (swz_chunk(rb, lchunk) << 3));
+  }
+#pragma unroll
+  for (int f = 0; f < MF; ++f) {
+    int ra = wm * MROWS + f * 16 + lrow;
+    afrag[f] = *reinterpret_cast<const bf16x8*>(
+        As + ra * BK + (swz_chunk(ra, lchunk) << 3));
+  }
+  if (PRIO) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+  for (int fm = 0; fm < MF; ++fm)
+#pragma unroll
+    for (int fn = 0; fn < 4; ++fn)
+      acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          afrag[fm], bfrag[fn], acc[fm][fn], 0, 0, 0);
+  if (PRIO) __builtin_amdgcn_s_setprio(0);
+}
+
+// bf16 epilogue: v = acc * alpha + bias[col], optional ReLU, then either
+// a plain store or (accum) a read-modify-write add — the dx fan-in:
+// exclusive tiles and a single split make the plain RMW race-free.
+// Accum is bool for a runtime choice, or std::true_type/false_type so
+// the unused branch never reaches the optimizer.
+template <int MF, int MROWS, class Accum>
+__device__ __forceinline__ void epilogue_bf16(
+    const f32x4 (&acc)[MF][4], bf16* C, const float* bias, int M, int N,
+    int ldc, int tile_m, int tile_n, int wm, int wn, int lane, int relu,
+    float alpha, Accum accum) {
+  int crow0 = tile_m + wm * MROWS + ((lane >> 4) << 2);
+  int ccol0 = tile_n + wn * 64 + (lane & 15);
+#pragma unroll
+  for (int fm = 0; fm < MF; ++fm) {
+#pragma unroll
+    for (int fn = 0; fn < 4; ++fn) {
+      int col = ccol0 + fn * 16;
+      if (col >= N) continue;
+      float badd = (bias != nullptr) ? bias[col] : 0.f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        int row = crow0 + fm * 16 + r;
+        if (row >= M) continue;
+        float v = acc[fm][fn][r] * alpha + badd;
+        if (relu && v < 0.f) v = 0.f;
+        int64_t off = (int64_t)row * ldc + col;
+        if (accum) v += bf2f(C[off]);
+        C[off] = f2bf(v);
+      }
+    }
+  }
+}
+
+// fp32 epilogue: STORE 1 = plain store (exclusive tiles), 2 = atomic add
+// (split-K).  BIAS adds the bias/ReLU terms of gemm_kernel; the wide dw
+// kernels have none (their bias slot carries the fused db output).
+template <int STORE, bool BIAS, int MF, int MROWS>
+__device__ __forceinline__ void epilogue_f32(
+    const f32x4 (&acc)[MF][4], float* C, const float* bias, int M, int N,
+    int ldc, int tile_m, int tile_n, int wm, int wn, int lane, int relu,
+    float alpha) {
+  int crow0 = tile_m + wm * MROWS + ((lane >> 4) << 2);
+  int ccol0 = tile_n + wn * 64 + (lane & 15);
+#pragma unroll
+  for (int fm = 0; fm < MF; ++fm) {
+#pragma unroll
+    for (int fn = 0; fn < 4; ++fn) {
+      int col = ccol0 + fn * 16;
+      if (col >= N) continue;
+      float badd = (BIAS && bias != nullptr) ? bias[col] : 0.f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        int row = crow0 + fm * 16 + r;
+        if (row >= M) continue;
+        float v = acc[fm][fn][r] * alpha;
+        if (BIAS) {
+          v += badd;
+          if (relu && v < 0.f) v = 0.f;
+        }
+        if (STORE == 1)
+          C[(int64_t)row * ldc + col] = v;
+        else
+          atomicAdd(C + (int64_t)row * ldc + col, v);
+      }
+    }
+  }
 }
 
 // ---------------------------------------------------------------- staging
@@ -80,6 +226,24 @@ __device__ __forceinline__ void stage_direct_guarded(
 // b16 scatters, and ~4-way instead of 16-way bank conflicts (row*64B
 // strides alias banks; the k-pair dimension now spreads them).
 // Fragment reads stay the standard swizzled b128 path.
+
+// the shared tail of the stage_trans_pair_* gathers: rows m0..m0+7 of
+// k-pair kp, (k, k+1) packed into one u32 per row
+__device__ __forceinline__ void write_kpairs(
+    unsigned short* lds, int m0, int kp, const unsigned short (&va)[8],
+    const unsigned short (&vb)[8]) {
+  int kk = kp * 2;
+  int chunk0 = kk >> 3, kin = kk & 7;    // position inside a 16B chunk
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    int row = m0 + j;
+    unsigned int packed = (unsigned int)va[j] |
+                          ((unsigned int)vb[j] << 16);
+    *reinterpret_cast<unsigned int*>(
+        lds + row * BK + (swz_chunk(row, chunk0) << 3) + kin) = packed;
+  }
+}
+
 __device__ __forceinline__ void stage_trans_pair_guarded(
     bf16* lds_, const bf16* g_, int row0, int rows, int ld,
     int k0, int kend, int tid, int nthreads = NTHREADS,
@@ -109,106 +273,8 @@ __device__ __forceinline__ void stage_trans_pair_guarded(
         for (int j = 0; j < 8; ++j) v[j] = 0;
       }
     }
-    int kk = kp * 2;
-    int chunk0 = kk >> 3, kin = kk & 7;  // position inside a 16B chunk
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      int row = m0 + j;
-      unsigned int packed = (unsigned int)va[j] |
-                            ((unsigned int)vb[j] << 16);
-      *reinterpret_cast<unsigned int*>(
-          lds + row * BK + (swz_chunk(row, chunk0) << 3) + kin) = packed;
-    }
+    write_kpairs(lds, m0, kp, va, vb);
   }
-}
-
-// --------------------------------------------------- wide-N dw kernel
-// Specialized for the skinny trans/trans weight-gradient GEMMs
-// (dw[Kout][Kcol] = dy^T @ col, K = N*P*Q huge): BN=256 halves the
-// A-operand re-read factor vs the 128x128 kernel; fp32 atomic split-K.
-
-constexpr int WBN = 256;
-constexpr int WNT = 512;  // 8 waves: 2 (M) x 4 (N)
-
-template <int STORE>  // 1 = plain fp32 store (no split-K), 2 = atomic
-__global__ __launch_bounds__(WNT, 1) void gemm_tt_wide_kernel(
-    const bf16* __restrict__ A, const bf16* __restrict__ B,
-    float* __restrict__ C, int M, int N, int K, int lda, int ldb, int ldc,
-    int ksplit, float alpha, float* __restrict__ db) {
-  __shared__ bf16 As[BM * BK];
-  __shared__ bf16 Bs[WBN * BK];
-
-  int mblocks = (M + BM - 1) / BM;
-  int nblocks = (N + WBN - 1) / WBN;
-  int bid = xcd_swizzle(blockIdx.x, mblocks * nblocks);
-  int bm = bid / nblocks, bn = bid % nblocks;
-  int tile_m = bm * BM, tile_n = bn * WBN;
-  int k_begin = blockIdx.y * ksplit;
-  int k_end = min(K, k_begin + ksplit);
-
-  int tid = threadIdx.x;
-  int wave = tid >> 6, lane = tid & 63;
-  int wm = wave >> 2, wn = wave & 3;     // 2x4 wave grid, 64x64 each
-  int lrow = lane & 15, lk8 = (lane >> 4) * 8;
-
-  f32x4 acc[4][4] = {};
-
-  // fused bias gradient: db[m] += sum_k A[k][m] — the A tiles are in
-  // LDS anyway; the bn==0 blocks of each k-split cover every k exactly
-  // once (colsum was 4-5%% of the AlexNet/GoogLeNet steps as separate
-  // ramp-bound launches over the same dy operand)
-  bool do_db = (db != nullptr) && (bn == 0);
-  for (int k0 = k_begin; k0 < k_end; k0 += BK) {
-    stage_trans_pair_guarded(As, A, tile_m, M, lda, k0, k_end, tid, WNT,
-                             BM);
-    stage_trans_pair_guarded(Bs, B, tile_n, N, ldb, k0, k_end, tid, WNT,
-                             WBN);
-    __syncthreads();
-    if (do_db && tid < BM && tile_m + tid < M) {
-      float acc_b = 0.f;
-      const bf16* row = As + tid * BK;
-#pragma unroll
-      for (int kk = 0; kk < BK; ++kk)
-        acc_b += bf2f(row[(swz_chunk(tid, kk >> 3) << 3) | (kk & 7)]);
-      atomicAdd(db + tile_m + tid, acc_b);
-    }
-    bf16x8 afrag[4], bfrag[4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      int ra = wm * 64 + f * 16 + lrow;
-      int rb = wn * 64 + f * 16 + lrow;
-      afrag[f] = *reinterpret_cast<const bf16x8*>(
-          As + ra * BK + (swz_chunk(ra, lk8 >> 3) << 3));
-      bfrag[f] = *reinterpret_cast<const bf16x8*>(
-          Bs + rb * BK + (swz_chunk(rb, lk8 >> 3) << 3));
-    }
-#pragma unroll
-    for (int fm = 0; fm < 4; ++fm)
-#pragma unroll
-      for (int fn = 0; fn < 4; ++fn)
-        acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            afrag[fm], bfrag[fn], acc[fm][fn], 0, 0, 0);
-    __syncthreads();
-  }
-
-  int crow0 = tile_m + wm * 64 + ((lane >> 4) << 2);
-  int ccol0 = tile_n + wn * 64 + (lane & 15);
-#pragma unroll
-  for (int fm = 0; fm < 4; ++fm)
-#pragma unroll
-    for (int fn = 0; fn < 4; ++fn) {
-      int col = ccol0 + fn * 16;
-      if (col >= N) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int row = crow0 + fm * 16 + r;
-        if (row >= M) continue;
-        if (STORE == 1)
-          C[(int64_t)row * ldc + col] = acc[fm][fn][r] * alpha;
-        else
-          atomicAdd(C + (int64_t)row * ldc + col, acc[fm][fn][r] * alpha);
-      }
-    }
 }
 
 // fast path: interior tile, aligned — direct-to-LDS DMA, 16 B per lane.
@@ -231,189 +297,7 @@ __device__ __forceinline__ void stage_direct_fast(
   }
 }
 
-// ------------------------------------------------------------------ kernel
-
-// WAVES=4: 2x2 wave grid of 64x64 (2 blocks/CU = 8 waves/CU);
-// WAVES=8: 4x2 grid of 32x64 (2 blocks/CU = 16 waves/CU — doubles the
-// wave-level parallelism hiding the staging/fragment latency).
-template <bool TRANS_A, bool TRANS_B, int STORE_MODE, int WAVES = 4>
-__global__ __launch_bounds__(WAVES * 64, 2) void gemm_kernel(
-    const bf16* __restrict__ A, const bf16* __restrict__ B,
-    void* __restrict__ C, const float* __restrict__ bias,
-    int M, int N, int K, int lda, int ldb, int ldc,
-    int ksplit, int relu, float alpha, int m_alloc, int n_alloc,
-    int64_t sA, int64_t sB, int64_t sC) {
-  // batched operation (blockIdx.z = batch index, strides in elements for
-  // A/B and BYTES for C since its type depends on STORE_MODE)
-  A += (int64_t)blockIdx.z * sA;
-  B += (int64_t)blockIdx.z * sB;
-  C = (void*)((char*)C + (int64_t)blockIdx.z * sC);
-  __shared__ bf16 Asb[2][BM * BK];
-  __shared__ bf16 Bsb[2][BN * BK];
-
-  int mblocks = (M + BM - 1) / BM;
-  int nblocks = (N + BN - 1) / BN;
-  int bid = xcd_swizzle(blockIdx.x, mblocks * nblocks);
-  int bm = bid / nblocks, bn = bid % nblocks;
-  int tile_m = bm * BM, tile_n = bn * BN;
-
-  int k_begin = blockIdx.y * ksplit;
-  int k_end = min(K, k_begin + ksplit);
-
-  constexpr int NT = WAVES * 64;
-  constexpr int MROWS = BM / (WAVES / 2);   // rows per wave (64 or 32)
-  constexpr int MF = MROWS / 16;            // m-fragments per wave
-  int tid = threadIdx.x;
-  int wave = tid >> 6, lane = tid & 63;
-  int wm = wave >> 1, wn = wave & 1;     // (WAVES/2) x 2 wave grid
-  int lrow = lane & 15, lk8 = (lane >> 4) * 8;
-
-  f32x4 acc[MF][4] = {};
-
-  // fast path only needs the STAGED rows to be readable: callers may
-  // over-allocate operand buffers (m_alloc/n_alloc >= M/N) so edge tiles
-  // stage junk rows whose outputs the epilogue guards discard
-  bool a_fast = !TRANS_A && (tile_m + BM <= m_alloc) && (lda % 8 == 0) &&
-                ((k_end - k_begin) % BK == 0) && (k_begin % 8 == 0);
-  bool b_fast = !TRANS_B && (tile_n + BN <= n_alloc) && (ldb % 8 == 0) &&
-                ((k_end - k_begin) % BK == 0) && (k_begin % 8 == 0);
-
-  if (a_fast && b_fast && (k_end - k_begin) >= 2 * BK) {
-    // Pipelined double-buffered path (interior aligned tiles): the next
-    // K-tile's direct-to-LDS DMA is issued BEFORE computing the current
-    // tile, and the pre-barrier wait is a COUNTED `s_waitcnt vmcnt(4)`
-    // (the 4 loads just issued stay in flight across the barrier) rather
-    // than __syncthreads' full drain — cdna_hip_programming.md §5.5
-    // T3/T4: "never drain vmcnt to 0 in the main loop".
-    int cur = 0;
-    stage_direct_fast<WAVES>(Asb[0], A, tile_m, lda, k_begin, tid);
-    stage_direct_fast<WAVES>(Bsb[0], B, tile_n, ldb, k_begin, tid);
-    for (int k0 = k_begin; k0 < k_end; k0 += BK) {
-      if (k0 + BK < k_end) {
-        stage_direct_fast<WAVES>(Asb[cur ^ 1], A, tile_m, lda, k0 + BK,
-                                 tid);
-        stage_direct_fast<WAVES>(Bsb[cur ^ 1], B, tile_n, ldb, k0 + BK,
-                                 tid);
-      }
-      // wait for the CURRENT tile's DMA loads; the prefetched tile's
-      // (2 per operand per wave at WAVES=4, 1 each at 8) remain
-      // outstanding
-      if (WAVES == 4)
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      const bf16* Asp = Asb[cur];
-      const bf16* Bsp = Bsb[cur];
-      bf16x8 afrag[MF], bfrag[4];
-#pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        int rb = wn * 64 + f * 16 + lrow;
-        bfrag[f] = *reinterpret_cast<const bf16x8*>(
-            Bsp + rb * BK + (swz_chunk(rb, lk8 >> 3) << 3));
-      }
-#pragma unroll
-      for (int f = 0; f < MF; ++f) {
-        int ra = wm * MROWS + f * 16 + lrow;
-        afrag[f] = *reinterpret_cast<const bf16x8*>(
-            Asp + ra * BK + (swz_chunk(ra, lk8 >> 3) << 3));
-      }
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int fm = 0; fm < MF; ++fm)
-#pragma unroll
-        for (int fn = 0; fn < 4; ++fn)
-          acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              afrag[fm], bfrag[fn], acc[fm][fn], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-      // all waves finish reading buf[cur] before the next iteration's
-      // stage overwrites it; the ds_reads completed before their MFMAs,
-      // so no counter drain is needed at this barrier
-      __builtin_amdgcn_s_barrier();
-      cur ^= 1;
-    }
-  } else {
-    bf16* As = Asb[0];
-    bf16* Bs = Bsb[0];
-    for (int k0 = k_begin; k0 < k_end; k0 += BK) {
-      if (a_fast) {
-        stage_direct_fast<WAVES>(As, A, tile_m, lda, k0, tid);
-      } else if (TRANS_A) {
-        stage_trans_pair_guarded(As, A, tile_m, M, lda, k0, k_end, tid,
-                                 NT);
-      } else {
-        stage_direct_guarded(As, A, tile_m, M, lda, k0, k_end, tid, NT);
-      }
-      if (b_fast) {
-        stage_direct_fast<WAVES>(Bs, B, tile_n, ldb, k0, tid);
-      } else if (TRANS_B) {
-        stage_trans_pair_guarded(Bs, B, tile_n, N, ldb, k0, k_end, tid,
-                                 NT);
-      } else {
-        stage_direct_guarded(Bs, B, tile_n, N, ldb, k0, k_end, tid, NT);
-      }
-      __syncthreads();
-
-      bf16x8 afrag[MF], bfrag[4];
-#pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        int rb = wn * 64 + f * 16 + lrow;
-        bfrag[f] = *reinterpret_cast<const bf16x8*>(
-            Bs + rb * BK + (swz_chunk(rb, lk8 >> 3) << 3));
-      }
-#pragma unroll
-      for (int f = 0; f < MF; ++f) {
-        int ra = wm * MROWS + f * 16 + lrow;
-        afrag[f] = *reinterpret_cast<const bf16x8*>(
-            As + ra * BK + (swz_chunk(ra, lk8 >> 3) << 3));
-      }
-#pragma unroll
-      for (int fm = 0; fm < MF; ++fm)
-#pragma unroll
-        for (int fn = 0; fn < 4; ++fn)
-          acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              afrag[fm], bfrag[fn], acc[fm][fn], 0, 0, 0);
-
-      __syncthreads();
-    }
-  }
-
-  // ------------------------------------------------------------- epilogue
-  int crow0 = tile_m + wm * MROWS + ((lane >> 4) << 2);
-  int ccol0 = tile_n + wn * 64 + (lane & 15);
-#pragma unroll
-  for (int fm = 0; fm < MF; ++fm) {
-#pragma unroll
-    for (int fn = 0; fn < 4; ++fn) {
-      int col = ccol0 + fn * 16;
-      if (col >= N) continue;
-      float badd = (bias != nullptr) ? bias[col] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int row = crow0 + fm * 16 + r;
-        if (row >= M) continue;
-        float v = acc[fm][fn][r] * alpha + badd;
-        if (relu && v < 0.f) v = 0.f;
-        int64_t off = (int64_t)row * ldc + col;
-        if (STORE_MODE == 0) {
-          reinterpret_cast<bf16*>(C)[off] = f2bf(v);
-        } else if (STORE_MODE == 3) {
-          // bf16 read-modify-write accumulate (dx fan-in; exclusive
-          // tiles, single split -> race-free)
-          bf16* p = reinterpret_cast<bf16*>(C) + off;
-          *p = f2bf(v + bf2f(*p));
-        } else if (STORE_MODE == 1) {
-          reinterpret_cast<float*>(C)[off] = v;
-        } else {
-          atomicAdd(reinterpret_cast<float*>(C) + off, v);
-        }
-      }
-    }
-  }
-}
-
-// ------------------------------------------ implicit-im2col conv GEMMs
+// ----------------------------------------- implicit-im2col conv staging
 // The col matrix's 8-element k-runs (one (r,s) tap, 8 consecutive
 // channels) are contiguous channel spans of the NHWC input whenever
 // Cg % 8 == 0, so the GEMM stages its col operand straight from x —
@@ -537,16 +421,7 @@ __device__ __forceinline__ void stage_trans_pair_implicit(
         }
       }
     }
-    int kk = kp * 2;
-    int chunk0 = kk >> 3, kin = kk & 7;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      int row = m0 + j;
-      unsigned int packed = (unsigned int)va[j] |
-                            ((unsigned int)vb[j] << 16);
-      *reinterpret_cast<unsigned int*>(
-          lds + row * BK + (swz_chunk(row, chunk0) << 3) + kin) = packed;
-    }
+    write_kpairs(lds, m0, kp, va, vb);
   }
 }
 
@@ -679,17 +554,282 @@ __device__ __forceinline__ void stage_trans_pair_implicit_sc(
         }
       }
     }
-    int kk = kp * 2;
-    int chunk0 = kk >> 3, kin = kk & 7;
+    write_kpairs(lds, m0, kp, va, vb);
+  }
+}
+
+// ---------------------------------------------- wide-N trans/trans kernel
+// Specialized for the skinny trans/trans weight-gradient GEMMs
+// (dw[Kout][Kcol] = dy^T @ col, K = N*P*Q huge): BN=256 halves the
+// A-operand re-read factor vs the 128x128 kernel; fp32 atomic split-K.
+// The col operand (B) comes from one of three staging policies.
+
+constexpr int WBN = 256;
+constexpr int WNT = 512;  // 8 waves: 2 (M) x 4 (N)
+
+struct BGuarded {         // materialized [K][N] matrix
+  const bf16* B;
+  int ldb;
+  __device__ __forceinline__ void stage(bf16* lds, int row0, int N, int k0,
+                                        int kend, int tid) const {
+    stage_trans_pair_guarded(lds, B, row0, N, ldb, k0, kend, tid, WNT, WBN);
+  }
+};
+
+struct BImplicit {        // im2col gather from the NHWC input, Cg % 8 == 0
+  const bf16* X;
+  CGeom gm;
+  __device__ __forceinline__ void stage(bf16* lds, int row0, int, int k0,
+                                        int kend, int tid) const {
+    stage_trans_pair_implicit(lds, X, gm, row0, k0, kend, tid, WNT, WBN);
+  }
+};
+
+struct BImplicitSC {      // small-C contiguous-run gather
+  const bf16* X;
+  CGeom gm;
+  __device__ __forceinline__ void stage(bf16* lds, int row0, int, int k0,
+                                        int kend, int tid) const {
+    stage_trans_pair_implicit_sc(lds, X, gm, row0, k0, kend, tid, WNT, WBN);
+  }
+};
+
+template <int STORE, class BStage>  // STORE as in epilogue_f32
+__global__ __launch_bounds__(WNT, 1) void gemm_wide_tt_kernel(
+    const bf16* __restrict__ A, float* __restrict__ C, int M, int N, int K,
+    int lda, int ldc, int ksplit, float alpha, float* __restrict__ db,
+    BStage bstage) {
+  __shared__ bf16 As[BM * BK];
+  __shared__ bf16 Bs[WBN * BK];
+
+  Tile t = decode_tile<WBN>(M, N);
+  int tile_m = t.tile_m, tile_n = t.tile_n;
+  int k_begin = blockIdx.y * ksplit;
+  int k_end = min(K, k_begin + ksplit);
+
+  int tid = threadIdx.x;
+  int wave = tid >> 6, lane = tid & 63;
+  int wm = wave >> 2, wn = wave & 3;     // 2x4 wave grid, 64x64 each
+
+  f32x4 acc[4][4] = {};
+
+  // fused bias gradient: db[m] += sum_k A[k][m] — the A tiles are in
+  // LDS anyway; the bn==0 blocks of each k-split cover every k exactly
+  // once (colsum was 4-5%% of the AlexNet/GoogLeNet steps as separate
+  // ramp-bound launches over the same dy operand)
+  bool do_db = (db != nullptr) && (t.bn == 0);
+  for (int k0 = k_begin; k0 < k_end; k0 += BK) {
+    stage_trans_pair_guarded(As, A, tile_m, M, lda, k0, k_end, tid, WNT,
+                             BM);
+    bstage.stage(Bs, tile_n, N, k0, k_end, tid);
+    __syncthreads();
+    if (do_db && tid < BM && tile_m + tid < M) {
+      float acc_b = 0.f;
+      const bf16* row = As + tid * BK;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      int row = m0 + j;
-      unsigned int packed = (unsigned int)va[j] |
-                            ((unsigned int)vb[j] << 16);
-      *reinterpret_cast<unsigned int*>(
-          lds + row * BK + (swz_chunk(row, chunk0) << 3) + kin) = packed;
+      for (int kk = 0; kk < BK; ++kk)
+        acc_b += bf2f(row[(swz_chunk(tid, kk >> 3) << 3) | (kk & 7)]);
+      atomicAdd(db + tile_m + tid, acc_b);
+    }
+    load_frags_mfma<4, 64, false>(As, Bs, wm, wn, lane, acc);
+    __syncthreads();
+  }
+
+  epilogue_f32<STORE, false, 4, 64>(acc, C, nullptr, M, N, ldc, tile_m,
+                                    tile_n, wm, wn, lane, 0, alpha);
+}
+
+// ------------------------------------------------- pipelined K loop
+// Shared by the kernels whose operands are both staged by direct-to-LDS
+// DMA.  A ring of DEPTH LDS buffers, prefetching DEPTH/2 tiles ahead: the
+// DMA of tile t+PF is issued BEFORE computing tile t, and the pre-barrier
+// wait is a COUNTED `s_waitcnt vmcnt(N)` (the loads just issued stay in
+// flight across the barrier) rather than __syncthreads' full drain —
+// cdna_hip_programming.md §5.5 T3/T4: "never drain vmcnt to 0 in the
+// main loop".
+//   DEPTH=2: a trailing barrier keeps stage(t+1) off buf[t&1] until all
+//     waves finished reading it (the ds_reads completed before their
+//     MFMAs, so no counter drain is needed at that barrier).
+//   DEPTH=4: one barrier per tile — the buffer written at iter t+1 (slot
+//     (t+3)&3) was last read at iter t-1, and barrier_t separates them.
+//     65.5 KB of LDS, still 2 blocks/CU within CDNA4's 160 KB.
+// Needs k_end - k_begin to be a multiple of BK and at least two tiles:
+// with a single tile nothing is prefetched, fewer than N loads are ever
+// outstanding, and the counted wait would pass before the tile landed.
+
+struct ADirect {          // [rows][K] matrix
+  const bf16* A;
+  int row0, ld;
+  template <int WAVES>
+  __device__ __forceinline__ void stage(bf16* lds, int k0, int tid) const {
+    stage_direct_fast<WAVES>(lds, A, row0, ld, k0, tid);
+  }
+};
+
+struct AImplicit {        // im2col gather from the NHWC input
+  const bf16* X;
+  const bf16* zpage;
+  const CGeom& gm;
+  const int* rinfo;
+  template <int WAVES>
+  __device__ __forceinline__ void stage(bf16* lds, int k0, int tid) const {
+    stage_implicit_fast<WAVES>(lds, X, zpage, gm, rinfo, k0, tid);
+  }
+};
+
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+template <int WAVES, int DEPTH, class AStage>
+__device__ __forceinline__ void pipelined_loop(
+    bf16 (*Asb)[BM * BK], bf16 (*Bsb)[BN * BK], const AStage& astage,
+    const bf16* B, int tile_n, int ldb, int k_begin, int k_end, int tid,
+    int wm, int wn, int lane, f32x4 (&acc)[mfrags_of(WAVES)][4]) {
+  constexpr int PF = DEPTH / 2;              // tiles in flight ahead
+  // each wave issues 8/WAVES DMA loads per operand per tile; the PF
+  // prefetched tiles' loads stay outstanding while the current tile's
+  // are waited for
+  constexpr int VMCNT = PF * 2 * (8 / WAVES);
+#pragma unroll
+  for (int p = 0; p < PF; ++p)
+    if (p == 0 || k_begin + p * BK < k_end) {
+      astage.template stage<WAVES>(Asb[p], k_begin + p * BK, tid);
+      stage_direct_fast<WAVES>(Bsb[p], B, tile_n, ldb, k_begin + p * BK,
+                               tid);
+    }
+  int cur = 0;                               // ring slot of tile k0
+  for (int k0 = k_begin; k0 < k_end; k0 += BK) {
+    if (k0 + PF * BK < k_end) {
+      int nxt = (cur + PF) & (DEPTH - 1);
+      astage.template stage<WAVES>(Asb[nxt], k0 + PF * BK, tid);
+      stage_direct_fast<WAVES>(Bsb[nxt], B, tile_n, ldb, k0 + PF * BK,
+                               tid);
+    }
+    wait_vmcnt<VMCNT>();
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    load_frags_mfma<mfrags_of(WAVES), mrows_of(WAVES), true>(
+        Asb[cur], Bsb[cur], wm, wn, lane, acc);
+    if (DEPTH == 2) __builtin_amdgcn_s_barrier();
+    cur = (cur + 1) & (DEPTH - 1);
+  }
+}
+
+// ------------------------------------------------------------------ kernel
+
+// WAVES=4: 2x2 wave grid of 64x64 (2 blocks/CU = 8 waves/CU);
+// WAVES=8: 4x2 grid of 32x64 (2 blocks/CU = 16 waves/CU — doubles the
+// wave-level parallelism hiding the staging/fragment latency).
+// STORE_MODE: 0 = bf16 store, 3 = bf16 RMW accumulate, 1 = fp32 store,
+// 2 = fp32 atomic add (split-K).
+template <bool TRANS_A, bool TRANS_B, int STORE_MODE, int WAVES = 4>
+__global__ __launch_bounds__(WAVES * 64, 2) void gemm_kernel(
+    const bf16* __restrict__ A, const bf16* __restrict__ B,
+    void* __restrict__ C, const float* __restrict__ bias,
+    int M, int N, int K, int lda, int ldb, int ldc,
+    int ksplit, int relu, float alpha, int m_alloc, int n_alloc,
+    int64_t sA, int64_t sB, int64_t sC) {
+  // batched operation (blockIdx.z = batch index, strides in elements for
+  // A/B and BYTES for C since its type depends on STORE_MODE)
+  A += (int64_t)blockIdx.z * sA;
+  B += (int64_t)blockIdx.z * sB;
+  C = (void*)((char*)C + (int64_t)blockIdx.z * sC);
+  __shared__ bf16 Asb[2][BM * BK];
+  __shared__ bf16 Bsb[2][BN * BK];
+
+  Tile t = decode_tile<BN>(M, N);
+  int tile_m = t.tile_m, tile_n = t.tile_n;
+  int k_begin = blockIdx.y * ksplit;
+  int k_end = min(K, k_begin + ksplit);
+
+  constexpr int NT = WAVES * 64;
+  constexpr int MROWS = mrows_of(WAVES), MF = mfrags_of(WAVES);
+  int tid = threadIdx.x;
+  int wave = tid >> 6, lane = tid & 63;
+  int wm = wave >> 1, wn = wave & 1;     // (WAVES/2) x 2 wave grid
+
+  f32x4 acc[MF][4] = {};
+
+  // fast path only needs the STAGED rows to be readable: callers may
+  // over-allocate operand buffers (m_alloc/n_alloc >= M/N) so edge tiles
+  // stage junk rows whose outputs the epilogue guards discard
+  bool a_fast = !TRANS_A && (tile_m + BM <= m_alloc) && (lda % 8 == 0) &&
+                ((k_end - k_begin) % BK == 0) && (k_begin % 8 == 0);
+  bool b_fast = !TRANS_B && (tile_n + BN <= n_alloc) && (ldb % 8 == 0) &&
+                ((k_end - k_begin) % BK == 0) && (k_begin % 8 == 0);
+
+  if (a_fast && b_fast && (k_end - k_begin) >= 2 * BK) {
+    pipelined_loop<WAVES, 2>(Asb, Bsb, ADirect{A, tile_m, lda}, B, tile_n,
+                             ldb, k_begin, k_end, tid, wm, wn, lane, acc);
+  } else {
+    bf16* As = Asb[0];
+    bf16* Bs = Bsb[0];
+    for (int k0 = k_begin; k0 < k_end; k0 += BK) {
+      if (a_fast) {
+        stage_direct_fast<WAVES>(As, A, tile_m, lda, k0, tid);
+      } else if (TRANS_A) {
+        stage_trans_pair_guarded(As, A, tile_m, M, lda, k0, k_end, tid,
+                                 NT);
+      } else {
+        stage_direct_guarded(As, A, tile_m, M, lda, k0, k_end, tid, NT);
+      }
+      if (b_fast) {
+        stage_direct_fast<WAVES>(Bs, B, tile_n, ldb, k0, tid);
+      } else if (TRANS_B) {
+        stage_trans_pair_guarded(Bs, B, tile_n, N, ldb, k0, k_end, tid,
+                                 NT);
+      } else {
+        stage_direct_guarded(Bs, B, tile_n, N, ldb, k0, k_end, tid, NT);
+      }
+      __syncthreads();
+      load_frags_mfma<MF, MROWS, false>(As, Bs, wm, wn, lane, acc);
+      __syncthreads();
     }
   }
+
+  if (STORE_MODE == 0 || STORE_MODE == 3)
+    epilogue_bf16<MF, MROWS>(acc, reinterpret_cast<bf16*>(C), bias, M, N,
+                             ldc, tile_m, tile_n, wm, wn, lane, relu, alpha,
+                             std::bool_constant<STORE_MODE == 3>{});
+  else
+    epilogue_f32<STORE_MODE, true, MF, MROWS>(
+        acc, reinterpret_cast<float*>(C), bias, M, N, ldc, tile_m, tile_n,
+        wm, wn, lane, relu, alpha);
+}
+
+// ------------------------------------------------------ forward conv GEMMs
+
+// forward conv GEMM: C[NPQ, Kg] = im2col(x) @ Wr^T, bias+ReLU fused.
+// Always the pipelined loop: the implicit A staging zero-fills
+// k >= Kcol, so K runs over Kpad (32-aligned by the host) with no
+// guarded edge cases, and Wr's padded rows/columns are zero.
+template <int WAVES, int DEPTH>
+__global__ __launch_bounds__(WAVES * 64, 2) void gemm_conv_fwd_kernel(
+    const bf16* __restrict__ X, const bf16* __restrict__ B,
+    bf16* __restrict__ C, const float* __restrict__ bias,
+    const bf16* __restrict__ zpage,
+    int M, int N, int K, int ldb, int ldc, int relu, int accum,
+    CGeom gm) {
+  __shared__ bf16 Asb[DEPTH][BM * BK];
+  __shared__ bf16 Bsb[DEPTH][BN * BK];
+  __shared__ int rinfo[BM * 3];
+
+  Tile t = decode_tile<BN>(M, N);
+  int tid = threadIdx.x;
+  int wave = tid >> 6, lane = tid & 63;
+  int wm = wave >> 1, wn = wave & 1;
+
+  decode_rows(rinfo, gm, t.tile_m, M, BM, tid);
+  __syncthreads();
+
+  f32x4 acc[mfrags_of(WAVES)][4] = {};
+  pipelined_loop<WAVES, DEPTH>(Asb, Bsb, AImplicit{X, zpage, gm, rinfo}, B,
+                               t.tile_n, ldb, 0, K, tid, wm, wn, lane, acc);
+  epilogue_bf16<mfrags_of(WAVES), mrows_of(WAVES)>(
+      acc, C, bias, M, N, ldc, t.tile_m, t.tile_n, wm, wn, lane, relu, 1.f,
+      accum != 0);
 }
 
 // small-C forward conv GEMM: double-buffered __syncthreads pipeline
@@ -703,21 +843,14 @@ __global__ __launch_bounds__(WAVES * 64, 2) void gemm_conv_fwd_sc_kernel(
   __shared__ bf16 Bsb[2][BN * BK];
   __shared__ int rinfo[BM * 3];
 
-  int mblocks = (M + BM - 1) / BM;
-  int nblocks = (N + BN - 1) / BN;
-  int bid = xcd_swizzle(blockIdx.x, mblocks * nblocks);
-  int bm = bid / nblocks, bn = bid % nblocks;
-  int tile_m = bm * BM, tile_n = bn * BN;
-
+  Tile tl = decode_tile<BN>(M, N);
   constexpr int NT = WAVES * 64;
-  constexpr int MROWS = BM / (WAVES / 2);
-  constexpr int MF = MROWS / 16;
+  constexpr int MROWS = mrows_of(WAVES), MF = mfrags_of(WAVES);
   int tid = threadIdx.x;
   int wave = tid >> 6, lane = tid & 63;
   int wm = wave >> 1, wn = wave & 1;
-  int lrow = lane & 15, lk8 = (lane >> 4) * 8;
 
-  decode_rows(rinfo, gm, tile_m, M, BM, tid);
+  decode_rows(rinfo, gm, tl.tile_m, M, BM, tid);
   __syncthreads();
 
   f32x4 acc[MF][4] = {};
@@ -727,414 +860,22 @@ __global__ __launch_bounds__(WAVES * 64, 2) void gemm_conv_fwd_sc_kernel(
   // next iteration's stage(t+2) overwrites it
   int T = K / BK;
   stage_implicit_sc(Asb[0], X, gm, rinfo, 0, tid, NT);
-  stage_direct_fast<WAVES>(Bsb[0], B, tile_n, ldb, 0, tid);
+  stage_direct_fast<WAVES>(Bsb[0], B, tl.tile_n, ldb, 0, tid);
   __syncthreads();
   for (int t = 0; t < T; ++t) {
     if (t + 1 < T) {
       stage_implicit_sc(Asb[(t + 1) & 1], X, gm, rinfo, (t + 1) * BK,
                         tid, NT);
-      stage_direct_fast<WAVES>(Bsb[(t + 1) & 1], B, tile_n, ldb,
+      stage_direct_fast<WAVES>(Bsb[(t + 1) & 1], B, tl.tile_n, ldb,
                                (t + 1) * BK, tid);
     }
-    const bf16* Asp = Asb[t & 1];
-    const bf16* Bsp = Bsb[t & 1];
-    bf16x8 afrag[MF], bfrag[4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      int rb = wn * 64 + f * 16 + lrow;
-      bfrag[f] = *reinterpret_cast<const bf16x8*>(
-          Bsp + rb * BK + (swz_chunk(rb, lk8 >> 3) << 3));
-    }
-#pragma unroll
-    for (int f = 0; f < MF; ++f) {
-      int ra = wm * MROWS + f * 16 + lrow;
-      afrag[f] = *reinterpret_cast<const bf16x8*>(
-          Asp + ra * BK + (swz_chunk(ra, lk8 >> 3) << 3));
-    }
-#pragma unroll
-    for (int fm = 0; fm < MF; ++fm)
-#pragma unroll
-      for (int fn = 0; fn < 4; ++fn)
-        acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            afrag[fm], bfrag[fn], acc[fm][fn], 0, 0, 0);
+    load_frags_mfma<MF, MROWS, false>(Asb[t & 1], Bsb[t & 1], wm, wn, lane,
+                                      acc);
     __syncthreads();
   }
 
-  int crow0 = tile_m + wm * MROWS + ((lane >> 4) << 2);
-  int ccol0 = tile_n + wn * 64 + (lane & 15);
-#pragma unroll
-  for (int fm = 0; fm < MF; ++fm) {
-#pragma unroll
-    for (int fn = 0; fn < 4; ++fn) {
-      int col = ccol0 + fn * 16;
-      if (col >= N) continue;
-      float badd = (bias != nullptr) ? bias[col] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int row = crow0 + fm * 16 + r;
-        if (row >= M) continue;
-        float v = acc[fm][fn][r] + badd;
-        if (relu && v < 0.f) v = 0.f;
-        C[(int64_t)row * ldc + col] = f2bf(v);
-      }
-    }
-  }
-}
-
-// small-C dw trans/trans GEMM (B operand gathered contiguously from x)
-template <int STORE>
-__global__ __launch_bounds__(WNT, 1) void gemm_conv_dw_sc_kernel(
-    const bf16* __restrict__ A, const bf16* __restrict__ X,
-    float* __restrict__ C, int M, int N, int K, int lda, int ldc,
-    int ksplit, float alpha, float* __restrict__ db, CGeom gm) {
-  __shared__ bf16 As[BM * BK];
-  __shared__ bf16 Bs[WBN * BK];
-
-  int mblocks = (M + BM - 1) / BM;
-  int nblocks = (N + WBN - 1) / WBN;
-  int bid = xcd_swizzle(blockIdx.x, mblocks * nblocks);
-  int bm = bid / nblocks, bn = bid % nblocks;
-  int tile_m = bm * BM, tile_n = bn * WBN;
-  int k_begin = blockIdx.y * ksplit;
-  int k_end = min(K, k_begin + ksplit);
-
-  int tid = threadIdx.x;
-  int wave = tid >> 6, lane = tid & 63;
-  int wm = wave >> 2, wn = wave & 3;
-  int lrow = lane & 15, lk8 = (lane >> 4) * 8;
-
-  f32x4 acc[4][4] = {};
-  bool do_db = (db != nullptr) && (bn == 0);
-  for (int k0 = k_begin; k0 < k_end; k0 += BK) {
-    stage_trans_pair_guarded(As, A, tile_m, M, lda, k0, k_end, tid, WNT,
-                             BM);
-    stage_trans_pair_implicit_sc(Bs, X, gm, tile_n, k0, k_end, tid, WNT,
-                                 WBN);
-    __syncthreads();
-    if (do_db && tid < BM && tile_m + tid < M) {
-      float acc_b = 0.f;
-      const bf16* row = As + tid * BK;
-#pragma unroll
-      for (int kk = 0; kk < BK; ++kk)
-        acc_b += bf2f(row[(swz_chunk(tid, kk >> 3) << 3) | (kk & 7)]);
-      atomicAdd(db + tile_m + tid, acc_b);
-    }
-    bf16x8 afrag[4], bfrag[4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      int ra = wm * 64 + f * 16 + lrow;
-      int rb = wn * 64 + f * 16 + lrow;
-      afrag[f] = *reinterpret_cast<const bf16x8*>(
-          As + ra * BK + (swz_chunk(ra, lk8 >> 3) << 3));
-      bfrag[f] = *reinterpret_cast<const bf16x8*>(
-          Bs + rb * BK + (swz_chunk(rb, lk8 >> 3) << 3));
-    }
-#pragma unroll
-    for (int fm = 0; fm < 4; ++fm)
-#pragma unroll
-      for (int fn = 0; fn < 4; ++fn)
-        acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            afrag[fm], bfrag[fn], acc[fm][fn], 0, 0, 0);
-    __syncthreads();
-  }
-
-  int crow0 = tile_m + wm * 64 + ((lane >> 4) << 2);
-  int ccol0 = tile_n + wn * 64 + (lane & 15);
-#pragma unroll
-  for (int fm = 0; fm < 4; ++fm)
-#pragma unroll
-    for (int fn = 0; fn < 4; ++fn) {
-      int col = ccol0 + fn * 16;
-      if (col >= N) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int row = crow0 + fm * 16 + r;
-        if (row >= M) continue;
-        if (STORE == 1)
-          C[(int64_t)row * ldc + col] = acc[fm][fn][r] * alpha;
-        else
-          atomicAdd(C + (int64_t)row * ldc + col, acc[fm][fn][r] * alpha);
-      }
-    }
-}
-
-// forward conv GEMM: C[NPQ, Kg] = im2col(x) @ Wr^T, bias+ReLU fused.
-// Always the pipelined double-buffered loop: the implicit A staging
-// zero-fills k >= Kcol, so K runs over Kpad (32-aligned by the host)
-// with no guarded edge cases, and Wr's padded rows/columns are zero.
-template <int WAVES>
-__global__ __launch_bounds__(WAVES * 64, 2) void gemm_conv_fwd_kernel(
-    const bf16* __restrict__ X, const bf16* __restrict__ B,
-    bf16* __restrict__ C, const float* __restrict__ bias,
-    const bf16* __restrict__ zpage,
-    int M, int N, int K, int ldb, int ldc, int relu, int accum,
-    CGeom gm) {
-  __shared__ bf16 Asb[2][BM * BK];
-  __shared__ bf16 Bsb[2][BN * BK];
-  __shared__ int rinfo[BM * 3];
-
-  int mblocks = (M + BM - 1) / BM;
-  int nblocks = (N + BN - 1) / BN;
-  int bid = xcd_swizzle(blockIdx.x, mblocks * nblocks);
-  int bm = bid / nblocks, bn = bid % nblocks;
-  int tile_m = bm * BM, tile_n = bn * BN;
-
-  constexpr int NT = WAVES * 64;
-  constexpr int MROWS = BM / (WAVES / 2);
-  constexpr int MF = MROWS / 16;
-  int tid = threadIdx.x;
-  int wave = tid >> 6, lane = tid & 63;
-  int wm = wave >> 1, wn = wave & 1;
-  int lrow = lane & 15, lk8 = (lane >> 4) * 8;
-
-  decode_rows(rinfo, gm, tile_m, M, BM, tid);
-  __syncthreads();
-
-  f32x4 acc[MF][4] = {};
-  int cur = 0;
-  stage_implicit_fast<WAVES>(Asb[0], X, zpage, gm, rinfo, 0, tid);
-  stage_direct_fast<WAVES>(Bsb[0], B, tile_n, ldb, 0, tid);
-  for (int k0 = 0; k0 < K; k0 += BK) {
-    if (k0 + BK < K) {
-      stage_implicit_fast<WAVES>(Asb[cur ^ 1], X, zpage, gm, rinfo,
-                                 k0 + BK, tid);
-      stage_direct_fast<WAVES>(Bsb[cur ^ 1], B, tile_n, ldb, k0 + BK,
-                               tid);
-    }
-    if (WAVES == 4)
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    const bf16* Asp = Asb[cur];
-    const bf16* Bsp = Bsb[cur];
-    bf16x8 afrag[MF], bfrag[4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      int rb = wn * 64 + f * 16 + lrow;
-      bfrag[f] = *reinterpret_cast<const bf16x8*>(
-          Bsp + rb * BK + (swz_chunk(rb, lk8 >> 3) << 3));
-    }
-#pragma unroll
-    for (int f = 0; f < MF; ++f) {
-      int ra = wm * MROWS + f * 16 + lrow;
-      afrag[f] = *reinterpret_cast<const bf16x8*>(
-          Asp + ra * BK + (swz_chunk(ra, lk8 >> 3) << 3));
-    }
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int fm = 0; fm < MF; ++fm)
-#pragma unroll
-      for (int fn = 0; fn < 4; ++fn)
-        acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            afrag[fm], bfrag[fn], acc[fm][fn], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_s_barrier();
-    cur ^= 1;
-  }
-
-  int crow0 = tile_m + wm * MROWS + ((lane >> 4) << 2);
-  int ccol0 = tile_n + wn * 64 + (lane & 15);
-#pragma unroll
-  for (int fm = 0; fm < MF; ++fm) {
-#pragma unroll
-    for (int fn = 0; fn < 4; ++fn) {
-      int col = ccol0 + fn * 16;
-      if (col >= N) continue;
-      float badd = (bias != nullptr) ? bias[col] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int row = crow0 + fm * 16 + r;
-        if (row >= M) continue;
-        float v = acc[fm][fn][r] + badd;
-        if (relu && v < 0.f) v = 0.f;
-        int64_t off = (int64_t)row * ldc + col;
-        if (accum) v += bf2f(C[off]);   // dx fan-in: exclusive tiles,
-        C[off] = f2bf(v);               // so plain RMW is race-free
-      }
-    }
-  }
-}
-
-// quad-buffered variant: four LDS buffers (65.5 KB, still 2 blocks/CU
-// within CDNA4's 160 KB) let ONE barrier per k-tile replace the usual
-// two — the buffer written at iter t+1 (slot (t+3)&3) was last read at
-// iter t-1, and barrier_t separates them (a wave's ds_reads complete
-// before its MFMAs consume them, hence before it arrives at barrier_t).
-template <int WAVES>
-__global__ __launch_bounds__(WAVES * 64, 2) void gemm_conv_fwd_q_kernel(
-    const bf16* __restrict__ X, const bf16* __restrict__ B,
-    bf16* __restrict__ C, const float* __restrict__ bias,
-    const bf16* __restrict__ zpage,
-    int M, int N, int K, int ldb, int ldc, int relu, int accum,
-    CGeom gm) {
-  __shared__ bf16 Asb[4][BM * BK];
-  __shared__ bf16 Bsb[4][BN * BK];
-  __shared__ int rinfo[BM * 3];
-
-  int mblocks = (M + BM - 1) / BM;
-  int nblocks = (N + BN - 1) / BN;
-  int bid = xcd_swizzle(blockIdx.x, mblocks * nblocks);
-  int bm = bid / nblocks, bn = bid % nblocks;
-  int tile_m = bm * BM, tile_n = bn * BN;
-
-  constexpr int MROWS = BM / (WAVES / 2);
-  constexpr int MF = MROWS / 16;
-  int tid = threadIdx.x;
-  int wave = tid >> 6, lane = tid & 63;
-  int wm = wave >> 1, wn = wave & 1;
-  int lrow = lane & 15, lk8 = (lane >> 4) * 8;
-
-  decode_rows(rinfo, gm, tile_m, M, BM, tid);
-  __syncthreads();
-
-  f32x4 acc[MF][4] = {};
-  int T = K / BK;
-  stage_implicit_fast<WAVES>(Asb[0], X, zpage, gm, rinfo, 0, tid);
-  stage_direct_fast<WAVES>(Bsb[0], B, tile_n, ldb, 0, tid);
-  if (T > 1) {
-    stage_implicit_fast<WAVES>(Asb[1], X, zpage, gm, rinfo, BK, tid);
-    stage_direct_fast<WAVES>(Bsb[1], B, tile_n, ldb, BK, tid);
-  }
-  for (int t = 0; t < T; ++t) {
-    if (t + 2 < T) {
-      stage_implicit_fast<WAVES>(Asb[(t + 2) & 3], X, zpage, gm, rinfo,
-                                 (t + 2) * BK, tid);
-      stage_direct_fast<WAVES>(Bsb[(t + 2) & 3], B, tile_n, ldb,
-                               (t + 2) * BK, tid);
-    }
-    if (WAVES == 4)
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    const bf16* Asp = Asb[t & 3];
-    const bf16* Bsp = Bsb[t & 3];
-    bf16x8 afrag[MF], bfrag[4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      int rb = wn * 64 + f * 16 + lrow;
-      bfrag[f] = *reinterpret_cast<const bf16x8*>(
-          Bsp + rb * BK + (swz_chunk(rb, lk8 >> 3) << 3));
-    }
-#pragma unroll
-    for (int f = 0; f < MF; ++f) {
-      int ra = wm * MROWS + f * 16 + lrow;
-      afrag[f] = *reinterpret_cast<const bf16x8*>(
-          Asp + ra * BK + (swz_chunk(ra, lk8 >> 3) << 3));
-    }
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int fm = 0; fm < MF; ++fm)
-#pragma unroll
-      for (int fn = 0; fn < 4; ++fn)
-        acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            afrag[fm], bfrag[fn], acc[fm][fn], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  }
-
-  int crow0 = tile_m + wm * MROWS + ((lane >> 4) << 2);
-  int ccol0 = tile_n + wn * 64 + (lane & 15);
-#pragma unroll
-  for (int fm = 0; fm < MF; ++fm) {
-#pragma unroll
-    for (int fn = 0; fn < 4; ++fn) {
-      int col = ccol0 + fn * 16;
-      if (col >= N) continue;
-      float badd = (bias != nullptr) ? bias[col] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int row = crow0 + fm * 16 + r;
-        if (row >= M) continue;
-        float v = acc[fm][fn][r] + badd;
-        if (relu && v < 0.f) v = 0.f;
-        int64_t off = (int64_t)row * ldc + col;
-        if (accum) v += bf2f(C[off]);
-        C[off] = f2bf(v);
-      }
-    }
-  }
-}
-
-// dw trans/trans GEMM with the col operand gathered implicitly:
-// dw[Kg][Kcol] = dy^T @ im2col(x), optional fused db, split-K atomics
-// (STORE 2) or plain store (STORE 1, single split).
-template <int STORE>
-__global__ __launch_bounds__(WNT, 1) void gemm_conv_dw_kernel(
-    const bf16* __restrict__ A, const bf16* __restrict__ X,
-    float* __restrict__ C, int M, int N, int K, int lda, int ldc,
-    int ksplit, float alpha, float* __restrict__ db, CGeom gm) {
-  __shared__ bf16 As[BM * BK];
-  __shared__ bf16 Bs[WBN * BK];
-
-  int mblocks = (M + BM - 1) / BM;
-  int nblocks = (N + WBN - 1) / WBN;
-  int bid = xcd_swizzle(blockIdx.x, mblocks * nblocks);
-  int bm = bid / nblocks, bn = bid % nblocks;
-  int tile_m = bm * BM, tile_n = bn * WBN;
-  int k_begin = blockIdx.y * ksplit;
-  int k_end = min(K, k_begin + ksplit);
-
-  int tid = threadIdx.x;
-  int wave = tid >> 6, lane = tid & 63;
-  int wm = wave >> 2, wn = wave & 3;
-  int lrow = lane & 15, lk8 = (lane >> 4) * 8;
-
-  f32x4 acc[4][4] = {};
-  bool do_db = (db != nullptr) && (bn == 0);
-  for (int k0 = k_begin; k0 < k_end; k0 += BK) {
-    stage_trans_pair_guarded(As, A, tile_m, M, lda, k0, k_end, tid, WNT,
-                             BM);
-    stage_trans_pair_implicit(Bs, X, gm, tile_n, k0, k_end, tid, WNT,
-                              WBN);
-    __syncthreads();
-    if (do_db && tid < BM && tile_m + tid < M) {
-      float acc_b = 0.f;
-      const bf16* row = As + tid * BK;
-#pragma unroll
-      for (int kk = 0; kk < BK; ++kk)
-        acc_b += bf2f(row[(swz_chunk(tid, kk >> 3) << 3) | (kk & 7)]);
-      atomicAdd(db + tile_m + tid, acc_b);
-    }
-    bf16x8 afrag[4], bfrag[4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      int ra = wm * 64 + f * 16 + lrow;
-      int rb = wn * 64 + f * 16 + lrow;
-      afrag[f] = *reinterpret_cast<const bf16x8*>(
-          As + ra * BK + (swz_chunk(ra, lk8 >> 3) << 3));
-      bfrag[f] = *reinterpret_cast<const bf16x8*>(
-          Bs + rb * BK + (swz_chunk(rb, lk8 >> 3) << 3));
-    }
-#pragma unroll
-    for (int fm = 0; fm < 4; ++fm)
-#pragma unroll
-      for (int fn = 0; fn < 4; ++fn)
-        acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            afrag[fm], bfrag[fn], acc[fm][fn], 0, 0, 0);
-    __syncthreads();
-  }
-
-  int crow0 = tile_m + wm * 64 + ((lane >> 4) << 2);
-  int ccol0 = tile_n + wn * 64 + (lane & 15);
-#pragma unroll
-  for (int fm = 0; fm < 4; ++fm)
-#pragma unroll
-    for (int fn = 0; fn < 4; ++fn) {
-      int col = ccol0 + fn * 16;
-      if (col >= N) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int row = crow0 + fm * 16 + r;
-        if (row >= M) continue;
-        if (STORE == 1)
-          C[(int64_t)row * ldc + col] = acc[fm][fn][r] * alpha;
-        else
-          atomicAdd(C + (int64_t)row * ldc + col, acc[fm][fn][r] * alpha);
-      }
-    }
+  epilogue_bf16<MF, MROWS>(acc, C, bias, M, N, ldc, tl.tile_m, tl.tile_n,
+                           wm, wn, lane, relu, 1.f, std::false_type{});
 }
 
 // ---- tr16 semantics probe: fills LDS with elem index, every lane does
@@ -1165,6 +906,45 @@ void tr16_probe(float* out, int mode, hipStream_t stream) {
 
 // ------------------------------------------------------------------- host
 
+// 8-wave blocks win on skinny shapes (one of M/N <= 256: fc6 +12%,
+// conv2/conv5 fwd +6-7%, conv1 +6% measured) and lose on fat ones
+// (conv3 -15%); COS_GEMM_W8=0/1 forces either variant for A/B.
+static bool use_w8(int M, int N) {
+  static const int w8_env = [] {
+    const char* e = getenv("COS_GEMM_W8");
+    return e ? (e[0] == '1' ? 1 : 0) : -1;
+  }();
+  return (w8_env == -1) ? (M <= 256 || N <= 256) : (w8_env == 1);
+}
+
+// split-K block arithmetic: K elements per split (BK-aligned so split
+// boundaries fall on tile boundaries) and the resulting grid.y
+struct SplitK { int ksplit, zblocks; };
+
+static SplitK split_k(int K, int splitk) {
+  splitk = max(1, splitk);
+  int ksplit = (K + splitk - 1) / splitk;
+  ksplit = ((ksplit + BK - 1) / BK) * BK;
+  return {ksplit, (K + ksplit - 1) / ksplit};
+}
+
+// plain store only when asked for AND every output element is written
+// by exactly one block; atomics otherwise
+template <class BStage>
+static void launch_wide_tt(const bf16* A, float* C, int M, int N, int K,
+                           int lda, int ldc, int store_mode, SplitK sk,
+                           float alpha, float* db, BStage bstage,
+                           hipStream_t stream) {
+  int mblocks = (M + BM - 1) / BM, nblocks = (N + WBN - 1) / WBN;
+  dim3 grid(mblocks * nblocks, sk.zblocks);
+  if (store_mode == 1 && sk.zblocks == 1)
+    gemm_wide_tt_kernel<1><<<grid, WNT, 0, stream>>>(
+        A, C, M, N, K, lda, ldc, sk.ksplit, alpha, db, bstage);
+  else
+    gemm_wide_tt_kernel<2><<<grid, WNT, 0, stream>>>(
+        A, C, M, N, K, lda, ldc, sk.ksplit, alpha, db, bstage);
+}
+
 void gemm_bf16_batched(const void* A_, const void* B_, void* C,
                        const float* bias, int M, int N, int K, int lda,
                        int ldb, int ldc, bool trans_a, bool trans_b,
@@ -1176,24 +956,13 @@ void gemm_bf16_batched(const void* A_, const void* B_, void* C,
   const bf16* A = reinterpret_cast<const bf16*>(A_);
   const bf16* B = reinterpret_cast<const bf16*>(B_);
   int mblocks = (M + BM - 1) / BM, nblocks = (N + BN - 1) / BN;
-  splitk = max(1, splitk);
-  int ksplit = (K + splitk - 1) / splitk;
-  ksplit = ((ksplit + BK - 1) / BK) * BK;  // keep split boundaries BK-aligned
-  int zblocks = (K + ksplit - 1) / ksplit;
-  if (zblocks > 1 && store_mode != 2)
+  SplitK sk = split_k(K, splitk);
+  int ksplit = sk.ksplit;
+  if (sk.zblocks > 1 && store_mode != 2)
     throw std::runtime_error("gemm: split-K requires atomic store mode");
   // store_mode 3 = bf16 RMW accumulate (single split only)
-  dim3 grid(mblocks * nblocks, zblocks, batch);
+  dim3 grid(mblocks * nblocks, sk.zblocks, batch);
   dim3 block(NTHREADS);
-
-  // 8-wave blocks win on skinny shapes (one of M/N <= 256: fc6 +12%,
-  // conv2/conv5 fwd +6-7%, conv1 +6% measured) and lose on fat ones
-  // (conv3 -15%); COS_GEMM_W8=0/1 forces either variant for A/B.
-  static const int w8_env = [] {
-    const char* e = getenv("COS_GEMM_W8");
-    return e ? (e[0] == '1' ? 1 : 0) : -1;
-  }();
-  bool w8 = (w8_env == -1) ? (M <= 256 || N <= 256) : (w8_env == 1);
 
 #define COS_GEMM_CASE(TA, TB, SM)                                          \
   gemm_kernel<TA, TB, SM><<<grid, block, 0, stream>>>(                      \
@@ -1214,20 +983,14 @@ void gemm_bf16_batched(const void* A_, const void* B_, void* C,
   } while (0)
 
   if (trans_a && trans_b && store_mode >= 1 && N > 128 && batch == 1) {
-    int nb_w = (N + WBN - 1) / WBN;
-    dim3 gw(mblocks * nb_w, zblocks);
-    if (store_mode == 1)   // single-split: exclusive tiles, plain store
-      gemm_tt_wide_kernel<1><<<gw, WNT, 0, stream>>>(
-          A, B, reinterpret_cast<float*>(C), M, N, K, lda, ldb, ldc,
-          ksplit, alpha, const_cast<float*>(bias));
-    else
-      gemm_tt_wide_kernel<2><<<gw, WNT, 0, stream>>>(
-          A, B, reinterpret_cast<float*>(C), M, N, K, lda, ldb, ldc,
-          ksplit, alpha, const_cast<float*>(bias));   // bias = fused db
+    // bias = fused db
+    launch_wide_tt(A, reinterpret_cast<float*>(C), M, N, K, lda, ldc,
+                   store_mode, sk, alpha, const_cast<float*>(bias),
+                   BGuarded{B, ldb}, stream);
     return;
   }
   if (!trans_a && !trans_b) {
-    if (w8) {
+    if (use_w8(M, N)) {
       if (store_mode == 0)      COS_GEMM_CASE8(0);
       else if (store_mode == 1) COS_GEMM_CASE8(1);
       else if (store_mode == 3) COS_GEMM_CASE8(3);
@@ -1266,11 +1029,7 @@ void gemm_conv_fwd(const void* X, const void* B, void* C,
   CGeom gm = make_geom(geom);
   int mblocks = (M + BM - 1) / BM, nblocks = (N + BN - 1) / BN;
   dim3 grid(mblocks * nblocks);
-  static const int w8_env = [] {
-    const char* e = getenv("COS_GEMM_W8");
-    return e ? (e[0] == '1' ? 1 : 0) : -1;
-  }();
-  bool w8 = (w8_env == -1) ? (M <= 256 || N <= 256) : (w8_env == 1);
+  bool w8 = use_w8(M, N);
   static const int quad = [] {
     // COS_CONVQ: 0 = off, otherwise a max-K gate (1 = "all shapes").
     // Default 1152: same-box A/B is +2.2% CIFAR, neutral AlexNet/
@@ -1280,23 +1039,14 @@ void gemm_conv_fwd(const void* X, const void* B, void* C,
     int v = atoi(e);
     return v == 1 ? 1 << 30 : v;
   }();
-  if (quad && w8 && K >= 4 * BK && K <= quad) {
-    gemm_conv_fwd_q_kernel<8><<<grid, dim3(512), 0, stream>>>(
-        (const bf16*)X, (const bf16*)B, (bf16*)C, bias,
-        (const bf16*)zpage, M, N, K, ldb, ldc, relu ? 1 : 0,
-        accum ? 1 : 0, gm);
-    return;
-  }
-  if (w8)
-    gemm_conv_fwd_kernel<8><<<grid, dim3(512), 0, stream>>>(
-        (const bf16*)X, (const bf16*)B, (bf16*)C, bias,
-        (const bf16*)zpage, M, N, K, ldb, ldc, relu ? 1 : 0,
-        accum ? 1 : 0, gm);
-  else
-    gemm_conv_fwd_kernel<4><<<grid, dim3(256), 0, stream>>>(
-        (const bf16*)X, (const bf16*)B, (bf16*)C, bias,
-        (const bf16*)zpage, M, N, K, ldb, ldc, relu ? 1 : 0,
-        accum ? 1 : 0, gm);
+#define COS_CONV_FWD(WAVES, DEPTH)                                          \
+  gemm_conv_fwd_kernel<WAVES, DEPTH><<<grid, WAVES * 64, 0, stream>>>(      \
+      (const bf16*)X, (const bf16*)B, (bf16*)C, bias, (const bf16*)zpage,   \
+      M, N, K, ldb, ldc, relu ? 1 : 0, accum ? 1 : 0, gm)
+  if (quad && w8 && K >= 4 * BK && K <= quad) COS_CONV_FWD(8, 4);
+  else if (w8)                                COS_CONV_FWD(8, 2);
+  else                                        COS_CONV_FWD(4, 2);
+#undef COS_CONV_FWD
 }
 
 void gemm_conv_fwd_sc(const void* X, const void* B, void* C,
@@ -1306,12 +1056,7 @@ void gemm_conv_fwd_sc(const void* X, const void* B, void* C,
   CGeom gm = make_geom(geom);
   int mblocks = (M + BM - 1) / BM, nblocks = (N + BN - 1) / BN;
   dim3 grid(mblocks * nblocks);
-  static const int w8_env = [] {
-    const char* e = getenv("COS_GEMM_W8");
-    return e ? (e[0] == '1' ? 1 : 0) : -1;
-  }();
-  bool w8 = (w8_env == -1) ? (M <= 256 || N <= 256) : (w8_env == 1);
-  if (w8)
+  if (use_w8(M, N))
     gemm_conv_fwd_sc_kernel<8><<<grid, dim3(512), 0, stream>>>(
         (const bf16*)X, (const bf16*)B, (bf16*)C, bias, M, N, K, ldb,
         ldc, relu ? 1 : 0, gm);
@@ -1325,42 +1070,18 @@ void gemm_conv_dw_sc(const void* A, const void* X, float* C, int M,
                      int N, int K, int lda, int ldc, int store_mode,
                      int splitk, float alpha, float* db, const int* geom,
                      hipStream_t stream) {
-  CGeom gm = make_geom(geom);
-  splitk = max(1, splitk);
-  int ksplit = (K + splitk - 1) / splitk;
-  ksplit = ((ksplit + BK - 1) / BK) * BK;
-  int zblocks = (K + ksplit - 1) / ksplit;
-  int mblocks = (M + BM - 1) / BM, nblocks = (N + WBN - 1) / WBN;
-  dim3 grid(mblocks * nblocks, zblocks);
-  if (store_mode == 1 && zblocks == 1)
-    gemm_conv_dw_sc_kernel<1><<<grid, WNT, 0, stream>>>(
-        (const bf16*)A, (const bf16*)X, C, M, N, K, lda, ldc, ksplit,
-        alpha, db, gm);
-  else
-    gemm_conv_dw_sc_kernel<2><<<grid, WNT, 0, stream>>>(
-        (const bf16*)A, (const bf16*)X, C, M, N, K, lda, ldc, ksplit,
-        alpha, db, gm);
+  launch_wide_tt((const bf16*)A, C, M, N, K, lda, ldc, store_mode,
+                 split_k(K, splitk), alpha, db,
+                 BImplicitSC{(const bf16*)X, make_geom(geom)}, stream);
 }
 
 void gemm_conv_dw(const void* A, const void* X, float* C, int M, int N,
                   int K, int lda, int ldc, int store_mode, int splitk,
                   float alpha, float* db, const int* geom,
                   hipStream_t stream) {
-  CGeom gm = make_geom(geom);
-  splitk = max(1, splitk);
-  int ksplit = (K + splitk - 1) / splitk;
-  ksplit = ((ksplit + BK - 1) / BK) * BK;
-  int zblocks = (K + ksplit - 1) / ksplit;
-  int mblocks = (M + BM - 1) / BM, nblocks = (N + WBN - 1) / WBN;
-  dim3 grid(mblocks * nblocks, zblocks);
-  if (store_mode == 1 && zblocks == 1)
-    gemm_conv_dw_kernel<1><<<grid, WNT, 0, stream>>>(
-        (const bf16*)A, (const bf16*)X, C, M, N, K, lda, ldc, ksplit,
-        alpha, db, gm);
-  else
-    gemm_conv_dw_kernel<2><<<grid, WNT, 0, stream>>>(
-        (const bf16*)A, (const bf16*)X, C, M, N, K, lda, ldc, ksplit,
-        alpha, db, gm);
+  launch_wide_tt((const bf16*)A, C, M, N, K, lda, ldc, store_mode,
+                 split_k(K, splitk), alpha, db,
+                 BImplicit{(const bf16*)X, make_geom(geom)}, stream);
 }
 
 void gemm_bf16(const void* A_, const void* B_, void* C, const float* bias,

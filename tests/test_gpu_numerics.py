@@ -107,8 +107,30 @@ def test_gemm_splitk_atomic():
     # small-C implicit (contiguous-run staging) WITH padding: edge
     # slots take the per-element guard path
     dict(n=2, c=4, h=21, w=21, k=16, r=9, stride=2, pad=4, groups=1),
+    # NPQ=288 and Kout=264 both > 256: the 4-wave implicit forward kernel
+    dict(n=2, c=8, h=12, w=12, k=264, r=3, stride=1, pad=1, groups=1),
+    # Kpad=2400 > 1152: implicit dx through the 4-wave kernel, and the
+    # 8-wave double-buffered (non-quad) forward
+    dict(n=2, c=264, h=12, w=12, k=8, r=3, stride=1, pad=1, groups=1),
+    # NPQ=324, Kout=264: the 4-wave small-C forward kernel
+    dict(n=4, c=3, h=43, w=43, k=264, r=11, stride=4, pad=0, groups=1),
+    # NPQ=1125 -> split-K 2: implicit dw, atomic store
+    dict(n=5, c=24, h=15, w=15, k=48, r=3, stride=1, pad=1, groups=1),
+    # NPQ=1089 -> split-K 2: small-C dw, atomic store
+    dict(n=9, c=3, h=51, w=51, k=32, r=11, stride=4, pad=0, groups=1),
 ])
 def test_conv_forward_backward(case):
+    _check_conv(case)
+
+
+def test_conv_fused_db(monkeypatch):
+    # the bias gradient computed inside the wide dw GEMM (off by default)
+    monkeypatch.setenv("COS_FUSE_DB", "1")
+    _check_conv(dict(n=2, c=24, h=13, w=13, k=48, r=3, stride=1, pad=1,
+                     groups=1))
+
+
+def _check_conv(case):
     n, c, h, w = case["n"], case["c"], case["h"], case["w"]
     k, r, st, pd, g = (case["k"], case["r"], case["stride"], case["pad"],
                        case["groups"])

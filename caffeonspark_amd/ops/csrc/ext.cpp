@@ -38,6 +38,14 @@ void repack_weights(const int64_t* table, int ndesc, int64_t max_total,
 void dw_unpack_acc(const float* dwp, float* arena, int Kout, int Cg,
                    int R, int S, int Kpad, bool accumulate,
                    hipStream_t stream);
+void s2d_pack(const void* x, void* out, int N, int H, int W, int C, int st,
+              int ph, int pw, int Hp, int Wp, int64_t sN, int64_t sC,
+              int64_t sH, int64_t sW, hipStream_t stream);
+void s2d_pack_weight(const void* src, void* dst, int Kout, int Cg, int R,
+                     int S, int st, int Kpad, hipStream_t stream);
+void dw_unpack_s2d(const float* dwp, float* arena, int Kout, int Cg, int R,
+                   int S, int st, int Kpad, bool accumulate,
+                   hipStream_t stream);
 int lstm_persist_fwd(const void* xg, const void* w_hc, const void* cont,
                      void* h, float* c, float* act, void* h_in, float* hg,
                      int T, int N, int H, void* bar, hipStream_t stream);
@@ -433,6 +441,53 @@ void py_repack_weights(Tensor table, int64_t ndesc, int64_t max_total) {
                          cur_stream());
 }
 
+// space-to-depth pack: x is read in place through its element strides
+// (NCHW-contiguous, channels-last or a strided view); out is the dense
+// channels-last [N][Hp][Wp][st*st*C] buffer, fully overwritten
+void py_s2d_pack(Tensor x, Tensor out, int64_t st, int64_t ph, int64_t pw,
+                 int64_t Hp, int64_t Wp) {
+  CHECK_CUDA(x); CHECK_BF16(x); CHECK_CUDA(out); CHECK_BF16(out);
+  TORCH_CHECK(x.dim() == 4, "x must be 4-D");
+  int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  TORCH_CHECK(st >= 2 && ph >= 0 && pw >= 0, "bad s2d geometry");
+  TORCH_CHECK(out.is_contiguous() &&
+              out.numel() == N * Hp * Wp * st * st * C,
+              "out must be dense [N][Hp][Wp][st*st*C]");
+  cosamd::s2d_pack(x.data_ptr(), out.data_ptr(), (int)N, (int)H, (int)W,
+                   (int)C, (int)st, (int)ph, (int)pw, (int)Hp, (int)Wp,
+                   x.stride(0), x.stride(1), x.stride(2), x.stride(3),
+                   cur_stream());
+}
+
+void py_s2d_pack_weight(Tensor src, Tensor dst, int64_t Kout, int64_t Cg,
+                        int64_t R, int64_t S, int64_t st, int64_t Kpad) {
+  CHECK_CUDA(src); CHECK_BF16(src); CHECK_CUDA(dst); CHECK_BF16(dst);
+  int64_t Rp = (R + st - 1) / st, Sp = (S + st - 1) / st;
+  TORCH_CHECK(st >= 2 && src.is_contiguous() &&
+              src.numel() == Kout * Cg * R * S, "bad s2d weight source");
+  TORCH_CHECK(dst.is_contiguous() && dst.dim() == 2 &&
+              dst.size(0) >= Kout && dst.size(1) == Kpad &&
+              Kpad >= Rp * Sp * st * st * Cg, "bad s2d weight buffer");
+  cosamd::s2d_pack_weight(src.data_ptr(), dst.data_ptr(), (int)Kout,
+                          (int)Cg, (int)R, (int)S, (int)st, (int)Kpad,
+                          cur_stream());
+}
+
+void py_dw_unpack_s2d(Tensor dwp, Tensor arena, int64_t Kout, int64_t Cg,
+                      int64_t R, int64_t S, int64_t st, int64_t Kpad,
+                      bool accumulate) {
+  CHECK_CUDA(dwp); CHECK_F32(dwp); CHECK_CUDA(arena); CHECK_F32(arena);
+  int64_t Rp = (R + st - 1) / st, Sp = (S + st - 1) / st;
+  TORCH_CHECK(st >= 2 && dwp.is_contiguous() &&
+              dwp.numel() >= Kout * Kpad &&
+              Kpad >= Rp * Sp * st * st * Cg, "bad s2d dw buffer");
+  TORCH_CHECK(arena.is_contiguous() &&
+              arena.numel() == Kout * Cg * R * S, "bad s2d dw target");
+  cosamd::dw_unpack_s2d(dwp.data_ptr<float>(), arena.data_ptr<float>(),
+                        (int)Kout, (int)Cg, (int)R, (int)S, (int)st,
+                        (int)Kpad, accumulate, cur_stream());
+}
+
 int64_t py_lstm_persist_fwd(Tensor xg, Tensor w_hc, Tensor cont,
                             Tensor h, Tensor c, Tensor act, Tensor h_in,
                             Tensor hg, int64_t T, int64_t N, int64_t H,
@@ -632,6 +687,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("tr16_probe", &py_tr16_probe);
   m.def("repack_weights", &py_repack_weights);
   m.def("dw_unpack_acc", &py_dw_unpack_acc);
+  m.def("s2d_pack", &py_s2d_pack);
+  m.def("s2d_pack_weight", &py_s2d_pack_weight);
+  m.def("dw_unpack_s2d", &py_dw_unpack_s2d);
   m.def("lstm_persist_fwd", &py_lstm_persist_fwd);
   m.def("lstm_persist_bwd", &py_lstm_persist_bwd);
   m.def("bias_act_cast", &py_bias_act_cast);

@@ -111,12 +111,12 @@ _repack = {"items": [], "table": None, "max": 0, "epoch": 0, "dirty": False}
 
 
 def _repack_register(src, wrb, wrT, Kout, Cg, R, S, Kpad, wrF=None,
-                     k2p=0, G=1, Cgp=0):
+                     k2p=0, G=1, Cgp=0, st=0):
     _repack["items"].append((_weakref.ref(src), _weakref.ref(wrb),
                              None if wrT is None else _weakref.ref(wrT),
                              Kout, Cg, R, S, Kpad,
                              None if wrF is None else _weakref.ref(wrF),
-                             k2p, G, Cgp))
+                             k2p, G, Cgp, st))
     _repack["dirty"] = True
 
 
@@ -147,7 +147,7 @@ def refresh_packed_weights():
                          0 if wrT is None else wrT.data_ptr(),
                          Kout, Cg, R, S, Kpad,
                          0 if wrF is None else wrF.data_ptr(), it[9],
-                         it[10], it[11]])
+                         it[10], it[11], it[12]])
             mx = max(mx, Kout * R * S * Cg)
         _repack["table"] = torch.tensor(rows, dtype=torch.int64).to(
             live[0][2].device)
@@ -272,6 +272,20 @@ def conv2d_forward(x, w, b, stride, pad, dilation, groups, ctx=None,
                    and N * P * Q < (1 << 18)
                    and 256 <= Kcol < (1 << 20)
                    and bool(int(os.environ.get("COS_IMPLICIT_SC", "1"))))
+    # conv1-class layers with a stride (AlexNet/LRCN conv1: C=3, 11x11,
+    # stride 4) are served by the space-to-depth route below instead:
+    # rearranged to st*st*C channels they are a stride-1 convolution
+    # with C % 8 == 0, so the DMA-staged implicit kernels above take
+    # them and neither a col matrix nor the _sc register staging is
+    # needed.  The _sc kernels keep the small-C shapes that route does
+    # not cover (st*st*C % 8 != 0, stride 1, sh != sw).
+    s2d = None if implicit else _s2d_geom(N, C, R, S, P, Q, sh, sw, dil, G)
+    if s2d is not None:
+        return _conv2d_forward_s2d(x, w, b, s2d, (N, C, H, W, P, Q, R, S,
+                                                  sh, sw, ph, pw, dil, G,
+                                                  Cg, Kg, _pad8(Kcol),
+                                                  Kcol),
+                                   ctx, relu, out_into)
     # 32-aligned K keeps every k-tile on the pipelined fast path (and
     # bounds the implicit kernel's B reads); pad columns stay zero
     Kpad = _pad32(Kcol) if (implicit or implicit_sc) else _pad8(Kcol)
@@ -286,10 +300,13 @@ def conv2d_forward(x, w, b, stride, pad, dilation, groups, ctx=None,
     # must stay inside the buffer (extra rows are zero -> contribute 0)
     rows_w = max(_pad128(Kout), (G - 1) * Kg + _pad128(Kg))
     wrb = getattr(w, "_cos_wrb", None)
-    if wrb is None or wrb.shape != (rows_w, Kpad):
+    if wrb is None or wrb.shape != (rows_w, Kpad) \
+            or getattr(w, "_cos_wrb_s2d", 0):
         wrb = torch.zeros((rows_w, Kpad), dtype=torch.bfloat16,
                           device=x.device)
         w._cos_wrb = wrb
+        w._cos_wrb_s2d = 0
+        w._cos_register_epoch = None
         shadow = w if (w.dtype == torch.bfloat16 and
                        getattr(w, "_cos_stable", False)) \
             else getattr(w, "_cos_bf16", None)
@@ -344,21 +361,7 @@ def conv2d_forward(x, w, b, stride, pad, dilation, groups, ctx=None,
     bias_f = b.float().contiguous() if b is not None else None
 
     NPQ = N * P * Q
-    if out_into is not None:
-        # fused concat: write this conv's output directly into its
-        # channel window of the shared concat buffer (GEMM ldc = the
-        # concat's total channel count) — no concat copy ever happens
-        buf, c_off = out_into
-        Ctot = buf.shape[1]
-        y = buf[:, c_off:c_off + Kout]
-        y2 = buf.permute(0, 2, 3, 1).reshape(NPQ, Ctot)[:, c_off:]
-        ldc_out = Ctot
-    else:
-        y = torch.empty((N, Kout, P, Q), dtype=torch.bfloat16,
-                        device=x.device,
-                        memory_format=torch.channels_last)
-        y2 = y.permute(0, 2, 3, 1).reshape(NPQ, Kout)  # NHWC flat alias
-        ldc_out = Kout
+    y, y2, ldc_out = _conv_out(x.device, N, Kout, P, Q, out_into)
     # Winograd F(4x4,3x3) for stride-1 pad-1 3x3 convs: 2.25-4x fewer
     # MACs than im2col GEMM (SURVEY.md §3.6 "Winograd is a rebuild
     # addition").  The col matrix is then built lazily in backward (dW
@@ -376,6 +379,7 @@ def conv2d_forward(x, w, b, stride, pad, dilation, groups, ctx=None,
             ctx["xl"] = xl
             ctx["is_1x1"] = False
             ctx["wino"] = True
+            ctx["s2d"] = None
             ctx["shape"] = (N, C, H, W, P, Q, R, S, sh, sw, ph, pw, dil, G,
                             Cg, Kg, Kpad, Kcol)
             ctx["wr"] = None
@@ -424,11 +428,151 @@ def conv2d_forward(x, w, b, stride, pad, dilation, groups, ctx=None,
         ctx["is_1x1"] = is_1x1
         ctx["implicit"] = implicit and not is_1x1
         ctx["implicit_sc"] = implicit_sc
+        ctx["s2d"] = None
         ctx["shape"] = (N, C, H, W, P, Q, R, S, sh, sw, ph, pw, dil, G, Cg,
                         Kg, Kpad, Kcol)
         ctx["wr"] = wr
         ctx["w_ref"] = w
     return y
+
+
+def _conv_out(device, N, Kout, P, Q, out_into):
+    """Output tensor of a conv forward, its [NPQ, Kout] NHWC alias and
+    that alias's row stride."""
+    NPQ = N * P * Q
+    if out_into is not None:
+        # fused concat: write this conv's output directly into its
+        # channel window of the shared concat buffer (GEMM ldc = the
+        # concat's total channel count) — no concat copy ever happens
+        buf, c_off = out_into
+        Ctot = buf.shape[1]
+        y = buf[:, c_off:c_off + Kout]
+        y2 = buf.permute(0, 2, 3, 1).reshape(NPQ, Ctot)[:, c_off:]
+        return y, y2, Ctot
+    y = torch.empty((N, Kout, P, Q), dtype=torch.bfloat16, device=device,
+                    memory_format=torch.channels_last)
+    y2 = y.permute(0, 2, 3, 1).reshape(NPQ, Kout)  # NHWC flat alias
+    return y, y2, Kout
+
+
+# ---- space-to-depth route.  A stride-st convolution over C channels is
+# a stride-1, pad-0 R'xS' convolution (R' = ceil(R/st), S' = ceil(S/st))
+# over the C' = st*st*C channels of
+#   X'[n][h'][w'][(dy*st+dx)*C + c] = x[n][c][st*h'+dy-ph][st*w'+dx-pw]
+# (H' = P+R'-1, W' = Q+S'-1; zero outside the image), with the weight
+# columns in the matching order and zero "phantom" taps where
+# st*r'+dy >= R or st*s'+dx >= S.  AlexNet conv1 (3ch 11x11/4, K=363)
+# becomes 48ch 3x3/1 (K=432): one 80 MB pack pass replaces the 570 MB
+# col matrix that was written once and read twice per step.
+
+def _s2d_geom(N, C, R, S, P, Q, sh, sw, dil, G):
+    """(st, R', S', C', H', W', Kcol', Kpad') when the layer takes the
+    space-to-depth route, else None."""
+    if not (G == 1 and dil == 1 and sh == sw and sh >= 2 and C % 8 != 0
+            and P > 0 and Q > 0):
+        return None
+    st = sh
+    Cp = st * st * C
+    Rp, Sp = -(-R // st), -(-S // st)
+    Kcol_s = Rp * Sp * Cp
+    # Kpad' > 128: the forward pipeline needs >= 2 k-tiles and the dw
+    # needs the wide TT kernel; NPQ bound = the kernels' magic divide
+    if Cp % 8 != 0 or N * P * Q >= (1 << 20) or _pad32(Kcol_s) <= 128 \
+            or Kcol_s >= (1 << 20):
+        return None
+    if os.environ.get("COS_S2D", "1") == "0":
+        return None
+    return (st, Rp, Sp, Cp, P + Rp - 1, Q + Sp - 1, Kcol_s, _pad32(Kcol_s))
+
+
+def _s2d_weight(w, Kout, C, R, S, st, Kpad_s, device):
+    """The forward GEMM's B operand in the space-to-depth column order,
+    cached on the weight; maintained by the fused per-step repack for
+    solver-managed weights, packed inline otherwise."""
+    rows_w = _pad128(Kout)
+    wrb = getattr(w, "_cos_wrb", None)
+    if wrb is None or wrb.shape != (rows_w, Kpad_s) \
+            or getattr(w, "_cos_wrb_s2d", 0) != st:
+        wrb = torch.zeros((rows_w, Kpad_s), dtype=torch.bfloat16,
+                          device=device)
+        w._cos_wrb = wrb
+        w._cos_wrb_s2d = st
+        w._cos_register_epoch = None
+        shadow = w if (w.dtype == torch.bfloat16 and
+                       getattr(w, "_cos_stable", False)) \
+            else getattr(w, "_cos_bf16", None)
+        if shadow is not None and shadow.is_contiguous():
+            _repack_register(shadow, wrb, None, Kout, C, R, S, Kpad_s,
+                             st=st)
+            w._cos_register_epoch = _repack["epoch"]
+    reg_epoch = getattr(w, "_cos_register_epoch", None)
+    if reg_epoch is None or _repack["epoch"] <= reg_epoch:
+        _ext.s2d_pack_weight(_as_bf16(w).contiguous(), wrb, Kout, C, R, S,
+                             st, Kpad_s)
+    return wrb
+
+
+def _conv2d_forward_s2d(x, w, b, s2d, shape, ctx, relu, out_into):
+    (N, C, H, W, P, Q, R, S, sh, sw, ph, pw, dil, G, Cg, Kg, Kpad,
+     Kcol) = shape
+    st, Rp, Sp, Cp, Hp, Wp, Kcol_s, Kpad_s = s2d
+    Kout = Kg
+    wrb = _s2d_weight(w, Kout, C, R, S, st, Kpad_s, x.device)
+    # the pack reads x in place through its strides (no _cl() pass) and
+    # writes every element of X', so no memset; it is rebuilt on every
+    # call — a training input changes every step
+    xs = torch.empty((N, Hp, Wp, Cp), dtype=torch.bfloat16,
+                     device=x.device)
+    _ext.s2d_pack(x, xs, st, ph, pw, Hp, Wp)
+    bias_f = b.float().contiguous() if b is not None else None
+    NPQ = N * P * Q
+    y, y2, ldc_out = _conv_out(x.device, N, Kout, P, Q, out_into)
+    geom = [Hp, Wp, Cp, P, Q, 1, 1, 0, 0, 1, Sp, 0, Cp, Kcol_s]
+    _ext.gemm_conv_fwd(xs, wrb, y2, bias_f, _zpage(x.device), NPQ, Kout,
+                       Kpad_s, Kpad_s, ldc_out, relu, False, geom)
+    if ctx is not None:
+        ctx["col"] = None
+        ctx["xl"] = None
+        ctx["is_1x1"] = False
+        ctx["wino"] = False
+        ctx["implicit"] = False
+        ctx["implicit_sc"] = False
+        ctx["s2d"] = s2d
+        ctx["xs2d"] = xs
+        ctx["shape"] = shape
+        ctx["wr"] = None
+        ctx["w_ref"] = w
+    return y
+
+
+def _conv_dw_s2d(ctx, dyg, ld_dy, dw_out):
+    """dW on the space-to-depth route: the implicit dw GEMM over
+    (dy, X') followed by the unpack to caffe layout."""
+    (N, C, H, W, P, Q, R, S, sh, sw, ph, pw, dil, G, Cg, Kg, Kpad,
+     Kcol) = ctx["shape"]
+    st, Rp, Sp, Cp, Hp, Wp, Kcol_s, Kpad_s = ctx["s2d"]
+    Kout, NPQ = Kg, N * P * Q
+    xs = ctx["xs2d"]
+    sk_tt = _splitk_tt(Kout, Kpad_s, NPQ)
+    if sk_tt == 1:
+        dwp = torch.empty((Kout, Kpad_s), dtype=torch.float32,
+                          device=xs.device)
+        store_dw = 1
+    else:
+        dwp = _scratch_buf((Kout, Kpad_s), torch.float32, xs.device)
+        store_dw = 2
+    geom = [Hp, Wp, Cp, P, Q, 1, 1, 0, 0, 1, Sp, 0, Cp, Kcol_s]
+    _ext.gemm_conv_dw(dyg, xs, dwp, None, Kout, Kpad_s, NPQ, ld_dy,
+                      Kpad_s, store_dw, sk_tt, 1.0, geom)
+    if dw_out is not None and dw_out.dtype == torch.float32 \
+            and dw_out.is_contiguous() \
+            and tuple(dw_out.shape) == (Kout, C, R, S):
+        dw = dw_out
+    else:
+        dw = torch.empty((Kout, C, R, S), dtype=torch.float32,
+                         device=xs.device)
+    _ext.dw_unpack_s2d(dwp, dw, Kout, C, R, S, st, Kpad_s, False)
+    return dw
 
 
 def _wino_run(xl, w, b, y, N, P, Q, C, K, relu, flip=False):
@@ -468,6 +612,7 @@ def conv2d_backward(x, w, dy, stride, pad, dilation, groups,
     wino = ctx.get("wino", False)
     implicit = ctx.get("implicit", False)
     implicit_sc = ctx.get("implicit_sc", False)
+    s2d = ctx.get("s2d")
     # implicit dw needs the wide TT kernel (N > 128); otherwise — and
     # for Winograd forward — materialize the col matrix lazily
     dw_implicit = implicit and Kpad > 128 and \
@@ -475,7 +620,7 @@ def conv2d_backward(x, w, dy, stride, pad, dilation, groups,
     dw_implicit_sc = implicit_sc and Kpad > 128 and \
         bool(int(os.environ.get("COS_DW_TT", "1")))
     if need_dw and col is None and not is_1x1 and not dw_implicit \
-            and not dw_implicit_sc:
+            and not dw_implicit_sc and not s2d:
         col = torch.empty((G, N * P * Q, Kpad), dtype=torch.bfloat16,
                           device=dy.device)
         for g in range(G):
@@ -515,13 +660,15 @@ def conv2d_backward(x, w, dy, stride, pad, dilation, groups,
     # the bn==0 blocks doing the extra LDS column pass become the
     # kernel's stragglers, costing more than the separate ramp-bound
     # colsum launches saved.  Kept behind COS_FUSE_DB=1 for evidence.
-    fuse_db = bias and need_dw and Kpad > 128 and \
+    fuse_db = bias and need_dw and Kpad > 128 and not s2d and \
         bool(int(os.environ.get("COS_DW_TT", "1"))) and \
         bool(int(os.environ.get("COS_FUSE_DB", "0")))
     if fuse_db:
         db = db_out if db_out is not None \
             else _scratch_buf((Kout,), torch.float32, dy.device)
-    if need_dw:
+    if need_dw and s2d:
+        dw = _conv_dw_s2d(ctx, _dyg(0), ld_dy, dw_out)
+    elif need_dw:
         # dw[kout][kpad] = sum_npq dy[npq][kout] * col[npq][kpad].
         # fused trans/trans dw (u32 k-pair staged; round 2): reads dy2/col
         # exactly once instead of transpose kernels + an extra HBM pass
@@ -662,6 +809,14 @@ def conv2d_backward(x, w, dy, stride, pad, dilation, groups,
                                    Cg, _pad32(k2), _pad32(k2), C, False,
                                    dx_acc, geom)
             return dx, dw, db
+        if s2d:
+            # the data gradient of a conv1-class layer is only asked for
+            # in tests (no net propagates into the data layer): build
+            # the original-layout packed weight here, on demand
+            wr = torch.zeros((_pad128(Kout), Kpad), dtype=torch.bfloat16,
+                             device=dy.device)[:Kout]
+            wr[:, :Kcol] = _as_bf16(ctx["w_ref"]).permute(0, 2, 3, 1) \
+                .reshape(Kout, Kcol)
         dcol = torch.empty((NPQ, Kpad), dtype=torch.bfloat16,
                            device=dy.device)
         for g in range(G):
@@ -669,7 +824,7 @@ def conv2d_backward(x, w, dy, stride, pad, dilation, groups,
             # packed weights — maintained by the fused repack kernel for
             # G==1, transposed here otherwise
             wrT = getattr(ctx.get("w_ref"), "_cos_wrT", None) \
-                if G == 1 else None
+                if G == 1 and not s2d else None
             if wrT is None:
                 wrT = _transpose(wr[g * Kg:(g + 1) * Kg].contiguous())
             _gemm(_dyg(g), wrT, dcol, None,

@@ -47,6 +47,9 @@ class Config:
         a("-embeddingDFDir", dest="embeddingDFDir", default="")
         a("-transform_thread_per_device", dest="transform_threads",
           type=int, default=1)
+        a("-transform_on_device", dest="transform_on_device",
+          action="store_true",
+          help="crop/mirror/mean/scale image batches on the device")
         a("-dtype", dest="dtype_name", default="",
           help="compute dtype: bf16|fp32 (default: bf16 on GPU)")
         ns, _ = p.parse_known_args(args or [])

@@ -189,6 +189,18 @@ class CaffeProcessor:
 
     @staticmethod
     def _reset_layer(dl, batch) -> None:
+        # a batch produced on a source's feed stream (-transform_on_device)
+        # carries the event recorded after its transform kernel: order the
+        # consumer's stream behind it, and tell the allocator that stream
+        # uses the tensors, before the layer adopts them
+        ready = getattr(batch, "ready", None)
+        if ready is not None:
+            import torch
+            cur = torch.cuda.current_stream(batch[0].device)
+            cur.wait_event(ready)
+            for t in batch:
+                if t.is_cuda:
+                    t.record_stream(cur)
         adapter = get_input_adapter(type(dl).TYPE)
         if adapter is not None:
             adapter(dl, batch)

@@ -191,6 +191,7 @@ bias_add = _dispatch("bias_add")
 sgd_update = _dispatch("sgd_update")
 nesterov_update = _dispatch("nesterov_update")
 adam_update = _dispatch("adam_update")
+data_transform = _dispatch("data_transform")
 
 
 def gpu_op(name):

@@ -663,14 +663,16 @@ __global__ void embed_bwd_kernel(const float* __restrict__ idx,
 }
 
 // ----------------------------------------------------- softmax + NLL loss
-// x [N, C] bf16 -> prob fp32, per-row loss accumulated into loss[0],
-// valid count into count[0].  One wave per row.
+// x [N, C] bf16 -> prob fp32 and the per-row loss rowloss[N] (0 for an
+// ignored row), one wave per row.  A second, single-block kernel then sums
+// the rows into loss[0] and the valid count into count[0] in a fixed
+// order, so equal inputs give a bit-equal loss (a float atomicAdd per row
+// would depend on the order in which the waves arrive).
 
 __global__ void softmax_loss_fwd_kernel(
     const u16* __restrict__ x, const float* __restrict__ label,
-    float* __restrict__ prob, float* __restrict__ loss,
-    int* __restrict__ count, int64_t nrows, int C, int ignore,
-    int has_ignore) {
+    float* __restrict__ prob, float* __restrict__ rowloss,
+    int64_t nrows, int C, int ignore, int has_ignore) {
   int64_t row = (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x / 64);
   int lane = threadIdx.x & 63;
   if (row >= nrows) return;
@@ -692,11 +694,40 @@ __global__ void softmax_loss_fwd_kernel(
     pp[c] = __expf(ldbf(xp + c) - mx) * inv;
   if (lane == 0) {
     int lab = (int)label[row];
-    if (!(has_ignore && lab == ignore)) {
-      float lp = ldbf(xp + lab) - mx - __logf(sum);
-      atomicAdd(loss, -lp);
-      atomicAdd(count, 1);
+    float lp = 0.f;
+    if (!(has_ignore && lab == ignore))
+      lp = ldbf(xp + lab) - mx - __logf(sum);
+    rowloss[row] = -lp;
+  }
+}
+
+__global__ __launch_bounds__(256) void softmax_loss_sum_kernel(
+    const float* __restrict__ rowloss, const float* __restrict__ label,
+    float* __restrict__ loss, int* __restrict__ count, int64_t nrows,
+    int ignore, int has_ignore) {
+  __shared__ float ssum[256];
+  __shared__ int scnt[256];
+  float sum = 0.f;
+  int cnt = 0;
+  for (int64_t row = threadIdx.x; row < nrows; row += 256) {
+    if (!(has_ignore && (int)label[row] == ignore)) {
+      sum += rowloss[row];
+      ++cnt;
     }
+  }
+  ssum[threadIdx.x] = sum;
+  scnt[threadIdx.x] = cnt;
+  __syncthreads();
+  for (int off = 128; off; off >>= 1) {
+    if ((int)threadIdx.x < off) {
+      ssum[threadIdx.x] += ssum[threadIdx.x + off];
+      scnt[threadIdx.x] += scnt[threadIdx.x + off];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    loss[0] = ssum[0];
+    count[0] = scnt[0];
   }
 }
 
@@ -825,14 +856,17 @@ void embed_bwd(const float* idx, const void* dy, float* dw, int64_t n, int E,
 }
 
 void softmax_loss_fwd(const void* x, const float* label, float* prob,
-                      float* loss, int* count, int64_t nrows, int C,
-                      int ignore, bool has_ignore, hipStream_t stream) {
+                      float* rowloss, float* loss, int* count,
+                      int64_t nrows, int C, int ignore, bool has_ignore,
+                      hipStream_t stream) {
   int waves_per_block = 4;
   int64_t blocks = (nrows + waves_per_block - 1) / waves_per_block;
   unsigned grid = (unsigned)hmin<int64_t>(blocks, (int64_t)1 << 30);
   softmax_loss_fwd_kernel<<<grid, waves_per_block * 64, 0, stream>>>(
-      (const u16*)x, label, prob, loss, count, nrows, C, ignore,
+      (const u16*)x, label, prob, rowloss, nrows, C, ignore,
       has_ignore ? 1 : 0);
+  softmax_loss_sum_kernel<<<1, 256, 0, stream>>>(
+      rowloss, label, loss, count, nrows, ignore, has_ignore ? 1 : 0);
 }
 
 void softmax_loss_bwd(const float* prob, const float* label, void* dx,

@@ -43,6 +43,12 @@ void s2d_pack(const void* x, void* out, int N, int H, int W, int C, int st,
               int64_t sH, int64_t sW, hipStream_t stream);
 void s2d_pack_weight(const void* src, void* dst, int Kout, int Cg, int R,
                      int S, int st, int Kpad, hipStream_t stream);
+void data_transform(const void* src, int64_t src_bytes, const int64_t* table,
+                    const int64_t* table_host, int N, const float* mean,
+                    int mean_mode, int64_t mean_numel, int mC, int mH,
+                    int mW, float scale, void* out, bool out_bf16, int C,
+                    int oh, int ow, int64_t osN, int64_t osC, int64_t osH,
+                    int64_t osW, hipStream_t stream);
 void dw_unpack_s2d(const float* dwp, float* arena, int Kout, int Cg, int R,
                    int S, int st, int Kpad, bool accumulate,
                    hipStream_t stream);
@@ -149,8 +155,9 @@ void lstm_seq_bwd(const void* dy, const void* w_hcT, const void* cont,
                   float* dc_b, int T, int N, int H, int n_alloc_whcT,
                   hipStream_t stream);
 void softmax_loss_fwd(const void* x, const float* label, float* prob,
-                      float* loss, int* count, int64_t nrows, int C,
-                      int ignore, bool has_ignore, hipStream_t stream);
+                      float* rowloss, float* loss, int* count,
+                      int64_t nrows, int C, int ignore, bool has_ignore,
+                      hipStream_t stream);
 void softmax_loss_bwd(const float* prob, const float* label, void* dx,
                       float scale, int64_t nrows, int C, int ignore,
                       bool has_ignore, hipStream_t stream);
@@ -459,6 +466,57 @@ void py_s2d_pack(Tensor x, Tensor out, int64_t st, int64_t ph, int64_t pw,
                    cur_stream());
 }
 
+// device-side DataTransformer: src is the packed uint8 bytes of the batch,
+// table the [N,7] int64 rows (byte_offset, H, W, planar, h_off, w_off,
+// mirror) on the device and table_host the same rows on the host, where
+// they are validated before the launch; out is any [N,C,oh,ow] view,
+// written through its strides
+void py_data_transform(Tensor src, Tensor table, Tensor table_host,
+                       c10::optional<Tensor> mean, int64_t mean_mode,
+                       double scale, Tensor out) {
+  CHECK_CUDA(src); CHECK_CUDA(table); CHECK_CUDA(out);
+  TORCH_CHECK(src.scalar_type() == at::kByte && src.dim() == 1 &&
+              src.is_contiguous(), "src must be a dense 1-D uint8 buffer");
+  TORCH_CHECK(out.dim() == 4, "out must be 4-D");
+  TORCH_CHECK(out.scalar_type() == at::kBFloat16 ||
+              out.scalar_type() == at::kFloat, "out must be bf16 or fp32");
+  int64_t N = out.size(0);
+  TORCH_CHECK(table.scalar_type() == at::kLong && table.is_contiguous() &&
+              table.dim() == 2 && table.size(0) == N && table.size(1) == 7,
+              "table must be a dense [N,7] int64 tensor");
+  TORCH_CHECK(!table_host.is_cuda() &&
+              table_host.scalar_type() == at::kLong &&
+              table_host.is_contiguous() &&
+              table_host.sizes() == table.sizes(),
+              "table_host must be the host copy of table");
+  TORCH_CHECK(N < (1ll << 31) && out.size(1) < (1ll << 31) &&
+              out.size(2) < (1ll << 31) && out.size(3) < (1ll << 31),
+              "out too large");
+  const float* mptr = nullptr;
+  int64_t mnumel = 0;
+  int mC = 0, mH = 0, mW = 0;
+  if (mean_mode != 0) {
+    TORCH_CHECK(mean.has_value(), "mean_mode != 0 needs a mean");
+    const Tensor& m = mean.value();
+    CHECK_CUDA(m); CHECK_F32(m);
+    TORCH_CHECK(m.is_contiguous(), "mean must be contiguous");
+    if (mean_mode == 2) {
+      TORCH_CHECK(m.dim() == 3 && m.size(1) < (1ll << 31) &&
+                  m.size(2) < (1ll << 31), "mean image must be [C,H,W]");
+      mC = (int)m.size(0); mH = (int)m.size(1); mW = (int)m.size(2);
+    }
+    mptr = m.data_ptr<float>();
+    mnumel = m.numel();
+  }
+  cosamd::data_transform(
+      src.data_ptr(), src.numel(), table.data_ptr<int64_t>(),
+      table_host.data_ptr<int64_t>(), (int)N, mptr, (int)mean_mode, mnumel,
+      mC, mH, mW, (float)scale, out.data_ptr(),
+      out.scalar_type() == at::kBFloat16, (int)out.size(1),
+      (int)out.size(2), (int)out.size(3), out.stride(0), out.stride(1),
+      out.stride(2), out.stride(3), cur_stream());
+}
+
 void py_s2d_pack_weight(Tensor src, Tensor dst, int64_t Kout, int64_t Cg,
                         int64_t R, int64_t S, int64_t st, int64_t Kpad) {
   CHECK_CUDA(src); CHECK_BF16(src); CHECK_CUDA(dst); CHECK_BF16(dst);
@@ -588,11 +646,15 @@ void py_lstm_seq_bwd(Tensor dy, Tensor w_hcT, Tensor cont, Tensor h,
                        T, N, H, n_alloc, cur_stream());
 }
 
-void py_softmax_loss_fwd(Tensor x, Tensor label, Tensor prob, Tensor loss,
-                         Tensor count, int64_t ignore, bool has_ignore) {
-  CHECK_BF16(x); CHECK_F32(label); CHECK_F32(prob);
+void py_softmax_loss_fwd(Tensor x, Tensor label, Tensor prob,
+                         Tensor rowloss, Tensor loss, Tensor count,
+                         int64_t ignore, bool has_ignore) {
+  CHECK_BF16(x); CHECK_F32(label); CHECK_F32(prob); CHECK_F32(rowloss);
+  TORCH_CHECK(rowloss.is_contiguous() && rowloss.numel() >= x.size(0),
+              "rowloss must hold one value per row");
   cosamd::softmax_loss_fwd(x.data_ptr(), label.data_ptr<float>(),
-                           prob.data_ptr<float>(), loss.data_ptr<float>(),
+                           prob.data_ptr<float>(),
+                           rowloss.data_ptr<float>(), loss.data_ptr<float>(),
                            count.data_ptr<int>(), x.size(0), x.size(1),
                            (int)ignore, has_ignore, cur_stream());
 }
@@ -689,6 +751,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dw_unpack_acc", &py_dw_unpack_acc);
   m.def("s2d_pack", &py_s2d_pack);
   m.def("s2d_pack_weight", &py_s2d_pack_weight);
+  m.def("data_transform", &py_data_transform);
   m.def("dw_unpack_s2d", &py_dw_unpack_s2d);
   m.def("lstm_persist_fwd", &py_lstm_persist_fwd);
   m.def("lstm_persist_bwd", &py_lstm_persist_bwd);

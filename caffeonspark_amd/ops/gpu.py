@@ -1151,9 +1151,10 @@ def softmax_loss_forward(x, label, ignore_label, axis=1):
     x2 = x.reshape(-1, C).contiguous()
     lab = label.float().reshape(-1).contiguous()
     prob = torch.empty_like(x2, dtype=torch.float32)
+    rowloss = torch.empty(x2.shape[0], dtype=torch.float32, device=x.device)
     loss = torch.zeros(1, dtype=torch.float32, device=x.device)
     count = torch.zeros(1, dtype=torch.int32, device=x.device)
-    _ext.softmax_loss_fwd(x2, lab, prob, loss, count,
+    _ext.softmax_loss_fwd(x2, lab, prob, rowloss, loss, count,
                           ignore_label if ignore_label is not None else 0,
                           ignore_label is not None)
     cnt = int(count.item()) if ignore_label is not None else lab.numel()
@@ -1484,6 +1485,30 @@ def sgd_update_multi_arena(solver, rate, momentum, wd):
                           solver._seg_dm * wd, momentum, sh)
     if sh is not None:
         solver._shadow_synced = True
+
+
+def data_transform(src, table, mean, mean_mode, scale, C, oh, ow, dtype,
+                   channels_last, out=None, table_host=None):
+    """Device-side DataTransformer, one launch per batch (transform.hip).
+    The extension validates every table row on the host before it launches:
+    pass `table_host` (the rows `table` was uploaded from) to avoid reading
+    the device table back."""
+    if dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"data_transform: unsupported dtype {dtype}")
+    if table_host is None:
+        table_host = table.cpu()
+    N = table.shape[0]
+    if out is None:
+        out = torch.empty(
+            (N, C, oh, ow), dtype=dtype, device=src.device,
+            memory_format=torch.channels_last if channels_last
+            else torch.contiguous_format)
+    elif tuple(out.shape) != (N, C, oh, ow) or out.dtype != dtype:
+        raise ValueError(f"out must be {dtype} [{N},{C},{oh},{ow}]")
+    _ext.data_transform(src, table, table_host,
+                        mean if mean_mode else None, int(mean_mode),
+                        float(scale), out)
+    return out
 
 
 # --------------------------------------------------------------- registry

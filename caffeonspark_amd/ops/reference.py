@@ -323,6 +323,56 @@ def bias_add(x, b, axis=1):
     return x + b.reshape(shape)
 
 
+# ------------------------------------------------------- data transform
+
+def data_transform(src, table, mean, mean_mode, scale, C, oh, ow, dtype,
+                   channels_last, out=None, table_host=None):
+    """Batch DataTransformer (crop / mirror / mean / scale) over packed raw
+    uint8 images.  `src` is the 1-D byte buffer of all images back to back,
+    `table` one int64 row per image: (byte_offset, H, W, planar, h_off,
+    w_off, mirror), planar=1 for CHW bytes and 0 for HWC.  mean_mode 0: no
+    mean, 1: per-channel [C], 2: a [C,H,W] image indexed at the source
+    position.  Returns (or fills `out`, any [N,C,oh,ow] view) the batch in
+    `dtype`; fp32 arithmetic is one subtract and one multiply (skipped when
+    scale == 1), as DataTransformer.transform_one does it.  `table_host` is
+    an optional host copy of `table`, used for the bounds checks."""
+    rows = (table_host if table_host is not None else table).tolist()
+    N = len(rows)
+    if out is None:
+        out = torch.empty(
+            (N, C, oh, ow), dtype=dtype, device=src.device,
+            memory_format=torch.channels_last if channels_last
+            else torch.contiguous_format)
+    elif tuple(out.shape) != (N, C, oh, ow) or out.dtype != dtype:
+        raise ValueError(f"out must be {dtype} [{N},{C},{oh},{ow}]")
+    if mean_mode == 1 and mean.numel() != C:
+        raise ValueError("per-channel mean must have C values")
+    for n, (off, H, W, planar, h_off, w_off, mirror) in enumerate(rows):
+        if H <= 0 or W <= 0 or off < 0 or off + C * H * W > src.numel():
+            raise ValueError(f"image {n}: bytes outside src")
+        if h_off < 0 or h_off + oh > H or w_off < 0 or w_off + ow > W:
+            raise ValueError(f"image {n}: crop outside the image")
+        img = src[off:off + C * H * W]
+        img = img.view(C, H, W) if planar else img.view(H, W, C).permute(
+            2, 0, 1)
+        x = img.float()
+        if mean_mode == 1:
+            x = x - mean.reshape(C, 1, 1)
+        elif mean_mode == 2:
+            if tuple(mean.shape) != (C, H, W):
+                raise ValueError(
+                    f"image {n}: mean image shape {tuple(mean.shape)} "
+                    f"differs from the image's {(C, H, W)}")
+            x = x - mean
+        x = x[:, h_off:h_off + oh, w_off:w_off + ow]
+        if mirror:
+            x = x.flip(2)
+        if scale != 1.0:
+            x = x * scale
+        out[n].copy_(x)
+    return out
+
+
 # ------------------------------------------------------------------ optimizer
 
 def sgd_update(param, grad, momentum_buf, lr, momentum, weight_decay):

@@ -63,12 +63,16 @@ dispatcher = _Dispatcher()
 _TORCH_OK_ON_GPU = set()
 
 # Activation/compute ops of the DECLARED fp32 GPU path (`-dtype fp32`):
-# the hand-written CDNA4 kernels are bf16-compute/fp32-accumulate; exact
-# fp32 Caffe numerics instead run the reference torch impls on ROCm
-# (rocBLAS GEMMs, MIOpen conv — library calls, not hidden kernel
-# fallbacks; BASELINE.md states the per-config dtype policy).  Solver
-# update ops are excluded: the fused fp32-arena update kernels serve both
-# dtypes natively.
+# the bf16 CDNA4 kernels are bf16-compute/fp32-accumulate, so exact fp32
+# Caffe numerics take a route of their own.  Convolution and InnerProduct
+# (_FP32_NATIVE_ON_GPU below) have a hand-written fp32 path on the
+# f32-input MFMA (csrc/gemm_f32.hip) that COS_FP32_NATIVE selects; without
+# it they run the reference torch impls on ROCm, i.e. rocBLAS GEMMs and
+# MIOpen convolutions.  Every other op in this set always runs its
+# reference torch impl: elementwise, pooling, normalisation, softmax and
+# loss kernels of torch itself, no library GEMM (BASELINE.md states the
+# per-config dtype policy).  Solver update ops are excluded: the fused
+# fp32-arena update kernels serve both dtypes natively.
 _FP32_REF_ON_GPU = {
     "conv2d_forward", "conv2d_backward", "fc_forward", "fc_backward",
     "relu_forward", "relu_backward", "sigmoid_forward", "sigmoid_backward",
@@ -81,6 +85,14 @@ _FP32_REF_ON_GPU = {
     "lstm_unit_backward", "bn_forward_train", "bn_forward_infer",
     "bn_backward", "accuracy", "bias_add",
 }
+
+# fp32-route ops with a native fp32 HIP implementation, registered by
+# ops/gpu.py as `<name>_f32`.  COS_FP32_NATIVE (read per call) picks the
+# route: "1" native, "0" the library route above; unset = _FP32_NATIVE_DEFAULT
+# (the measured-faster of the two, BASELINE.md "Dtype policy").
+_FP32_NATIVE_ON_GPU = {"conv2d_forward", "conv2d_backward", "fc_forward",
+                       "fc_backward"}
+_FP32_NATIVE_DEFAULT = "0"
 
 # Ops whose fp32 routing can ALSO be decided by dtype sniffing when no net
 # has declared a mode (direct op calls in tests/pycaffe).  Backward ops
@@ -140,6 +152,11 @@ def _dispatch(name: str):
                         and name in _FP32_SNIFF_OK
                         and not _any_bf16(args))):
                 # declared fp32 GPU path (see _FP32_REF_ON_GPU docstring)
+                if name in _FP32_NATIVE_ON_GPU and os.environ.get(
+                        "COS_FP32_NATIVE", _FP32_NATIVE_DEFAULT) != "0":
+                    fn32 = dispatcher.gpu_impls.get(name + "_f32")
+                    if fn32 is not None:
+                        return fn32(*args, **kwargs)
                 return ref_fn(*args, **kwargs)
             fn = dispatcher.gpu_impls.get(name)
             if fn is not None:

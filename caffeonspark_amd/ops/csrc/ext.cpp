@@ -16,6 +16,18 @@ void gemm_bf16(const void* A, const void* B, void* C, const float* bias,
                bool trans_a, bool trans_b, int store_mode, int splitk,
                bool relu, float alpha, int m_alloc, int n_alloc,
                hipStream_t stream);
+void gemm_f32(const float* A, const float* B, float* C, const float* bias,
+              int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc,
+              bool trans_a, bool trans_b, int splitk, bool relu,
+              hipStream_t stream);
+void im2col_f32(const float* x, float* col, int N, int H, int W, int P,
+                int Q, int R, int S, int sh, int sw, int ph, int pw, int dh,
+                int dw, int c0, int Cg, int64_t sN, int64_t sC, int64_t sH,
+                int64_t sW, hipStream_t stream);
+void col2im_f32(const float* dcol, float* dx, int N, int H, int W, int P,
+                int Q, int R, int S, int sh, int sw, int ph, int pw, int dh,
+                int dw, int c0, int Cg, int64_t sN, int64_t sC, int64_t sH,
+                int64_t sW, hipStream_t stream);
 void gemm_conv_fwd(const void* X, const void* B, void* C,
                    const float* bias, const void* zpage, int M, int N,
                    int K, int ldb, int ldc, bool relu, bool accum,
@@ -193,6 +205,98 @@ void py_gemm(Tensor A, Tensor B, Tensor C, c10::optional<Tensor> bias,
       A.data_ptr(), B.data_ptr(), C.data_ptr(), bptr, (int)M, (int)N, (int)K, (int)lda, (int)ldb, (int)ldc,
       trans_a, trans_b, (int)store_mode, (int)splitk, relu, (float)alpha,
       (int)m_alloc, (int)n_alloc, cur_stream());
+}
+
+// elements addressable from t's first element to the end of its storage
+int64_t span_f32(const Tensor& t) {
+  return (int64_t)(t.storage().nbytes() / sizeof(float)) - t.storage_offset();
+}
+
+// fp32 GEMM on the f32 MFMA (gemm_f32.hip).  Same operand convention and
+// argument order as `gemm`, minus the bf16-only arguments.  A, B and C may be
+// row sub-views: only the leading dimensions describe them, so every
+// operand's extent is checked against its storage before the launch.
+void py_gemm_f32(Tensor A, Tensor B, Tensor C, c10::optional<Tensor> bias,
+                 int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
+                 int64_t ldc, bool trans_a, bool trans_b, int64_t splitk,
+                 bool relu) {
+  CHECK_CUDA(A); CHECK_CUDA(B); CHECK_CUDA(C);
+  CHECK_F32(A); CHECK_F32(B); CHECK_F32(C);
+  const int64_t lim = 1ll << 31;
+  TORCH_CHECK(M > 0 && N > 0 && K > 0 && M < lim && N < lim && K < lim,
+              "gemm_f32: bad M/N/K");
+  int64_t ar = trans_a ? K : M, ac = trans_a ? M : K;
+  int64_t br = trans_b ? K : N, bc = trans_b ? N : K;
+  TORCH_CHECK(lda >= ac && ldb >= bc && ldc >= N,
+              "gemm_f32: leading dimension smaller than the row");
+  TORCH_CHECK((ar - 1) * lda + ac <= span_f32(A), "gemm_f32: A too small");
+  TORCH_CHECK((br - 1) * ldb + bc <= span_f32(B), "gemm_f32: B too small");
+  TORCH_CHECK((M - 1) * ldc + N <= span_f32(C), "gemm_f32: C too small");
+  TORCH_CHECK(splitk >= 1 && splitk <= 65535, "gemm_f32: bad splitk");
+  TORCH_CHECK((N + 127) / 128 <= 65535, "gemm_f32: N too large");
+  const float* bptr = nullptr;
+  if (bias.has_value()) {
+    const Tensor& b = bias.value();
+    CHECK_CUDA(b); CHECK_F32(b);
+    TORCH_CHECK(b.is_contiguous() && b.numel() >= N,
+                "gemm_f32: bias must hold N contiguous floats");
+    bptr = b.data_ptr<float>();
+  }
+  cosamd::gemm_f32(A.data_ptr<float>(), B.data_ptr<float>(),
+                   C.data_ptr<float>(), bptr, (int)M, (int)N, (int)K, lda,
+                   ldb, ldc, trans_a, trans_b, (int)splitk, relu,
+                   cur_stream());
+}
+
+// fp32 im2col / col2im (gemm_f32.hip).  x / dx are logical-NCHW 4-D tensors
+// read or written through their strides; col is the dense
+// [N*P*Q][R*S*Cg] matrix (channel fastest) of channels c0 .. c0+Cg-1.
+void check_conv_f32(const Tensor& x, const Tensor& col, int64_t P, int64_t Q,
+                    int64_t R, int64_t S, int64_t sh, int64_t sw, int64_t ph,
+                    int64_t pw, int64_t dh, int64_t dw, int64_t c0,
+                    int64_t Cg) {
+  CHECK_CUDA(x); CHECK_CUDA(col); CHECK_F32(x); CHECK_F32(col);
+  TORCH_CHECK(x.dim() == 4, "x must be 4-D");
+  const int64_t lim = 1ll << 31;
+  int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  TORCH_CHECK(N > 0 && H > 0 && W > 0 && N < lim && H < lim && W < lim,
+              "bad input shape");
+  TORCH_CHECK(P > 0 && Q > 0 && R > 0 && S > 0 && sh > 0 && sw > 0 &&
+              ph >= 0 && pw >= 0 && dh > 0 && dw > 0 && c0 >= 0 && Cg > 0 &&
+              c0 + Cg <= C, "bad conv geometry");
+  TORCH_CHECK(N * P * Q < lim && Cg * R * S < lim, "conv too large");
+  int64_t last = 0;
+  for (int d = 0; d < 4; ++d) {
+    TORCH_CHECK(x.stride(d) >= 0, "negative stride");
+    last += (x.size(d) - 1) * x.stride(d);
+  }
+  TORCH_CHECK(last < span_f32(x), "x view exceeds its storage");
+  TORCH_CHECK(col.is_contiguous() && col.numel() >= N * P * Q * Cg * R * S,
+              "col too small");
+}
+
+void py_im2col_f32(Tensor x, Tensor col, int64_t P, int64_t Q, int64_t R,
+                   int64_t S, int64_t sh, int64_t sw, int64_t ph, int64_t pw,
+                   int64_t dh, int64_t dw, int64_t c0, int64_t Cg) {
+  check_conv_f32(x, col, P, Q, R, S, sh, sw, ph, pw, dh, dw, c0, Cg);
+  cosamd::im2col_f32(x.data_ptr<float>(), col.data_ptr<float>(),
+                     (int)x.size(0), (int)x.size(2), (int)x.size(3), (int)P,
+                     (int)Q, (int)R, (int)S, (int)sh, (int)sw, (int)ph,
+                     (int)pw, (int)dh, (int)dw, (int)c0, (int)Cg,
+                     x.stride(0), x.stride(1), x.stride(2), x.stride(3),
+                     cur_stream());
+}
+
+void py_col2im_f32(Tensor dcol, Tensor dx, int64_t P, int64_t Q, int64_t R,
+                   int64_t S, int64_t sh, int64_t sw, int64_t ph, int64_t pw,
+                   int64_t dh, int64_t dw, int64_t c0, int64_t Cg) {
+  check_conv_f32(dx, dcol, P, Q, R, S, sh, sw, ph, pw, dh, dw, c0, Cg);
+  cosamd::col2im_f32(dcol.data_ptr<float>(), dx.data_ptr<float>(),
+                     (int)dx.size(0), (int)dx.size(2), (int)dx.size(3),
+                     (int)P, (int)Q, (int)R, (int)S, (int)sh, (int)sw,
+                     (int)ph, (int)pw, (int)dh, (int)dw, (int)c0, (int)Cg,
+                     dx.stride(0), dx.stride(1), dx.stride(2), dx.stride(3),
+                     cur_stream());
 }
 
 void py_gemm_conv_fwd(Tensor X, Tensor B, Tensor C,
@@ -670,6 +774,9 @@ void py_softmax_loss_bwd(Tensor prob, Tensor label, Tensor dx, double scale,
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm", &py_gemm);
+  m.def("gemm_f32", &py_gemm_f32);
+  m.def("im2col_f32", &py_im2col_f32);
+  m.def("col2im_f32", &py_col2im_f32);
   m.def("relu_colsum_bwd", &py_relu_colsum_bwd);
   m.def("gemm_conv_fwd", &py_gemm_conv_fwd);
   m.def("gemm_conv_dw", &py_gemm_conv_dw);

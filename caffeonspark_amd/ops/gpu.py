@@ -947,6 +947,249 @@ def fc_backward(x, w, dy, need_dx=True, bias=True, dw_out=None,
     return dx, dw, db
 
 
+# ------------------------------------------------- exact-fp32 GEMM path
+#
+# `-dtype fp32` Convolution / InnerProduct on the f32-input MFMA
+# (csrc/gemm_f32.hip): fp32 in, fp32 accumulate, fp32 out — Caffe's own
+# numerics.  Signatures equal the reference's; ops/__init__ routes here
+# (`<op>_f32`) on the fp32 GPU path.
+
+def gemm_f32(A, B, C, bias, M, N, K, lda, ldb, ldc, trans_a=False,
+             trans_b=False, splitk=1, relu=False):
+    """C[M,N] = op(A)·op(B) (+bias[n]) (ReLU) in exact fp32.  A is [M,K]
+    ([K,M] if trans_a), B is [N,K] ([K,N] if trans_b); lda/ldb/ldc are row
+    strides in elements, so row sub-views pass as they are.  With
+    splitk > 1 the slices add atomically: the caller zeroes C first, and
+    ReLU cannot be fused."""
+    _ext.gemm_f32(A, B, C, bias, M, N, K, lda, ldb, ldc, trans_a, trans_b,
+                  splitk, relu)
+    return C
+
+
+def _splitk_f32(M: int, N: int, K: int) -> int:
+    """Split-K factor of the fp32 GEMM (128x128 tiles, 4-wave blocks).  As
+    `_splitk_for`: only grids that leave most of the 256 CUs idle split,
+    each slice keeps >= 256 of K, and ~2 blocks per CU bound the fp32
+    atomic traffic."""
+    tiles = ((M + 127) // 128) * ((N + 127) // 128)
+    if tiles >= 256 or K < 1024:
+        return 1
+    return max(1, min(K // 256, 512 // tiles))
+
+
+def _mat_f32(t):
+    """A 2-D tensor as (tensor, ld, stored_transposed) without a copy when
+    either axis is unit-stride; otherwise one contiguous copy."""
+    r, c = t.shape
+    s0, s1 = t.stride()
+    if (s1 == 1 or c == 1) and (s0 >= c or r == 1):
+        return t, max(s0, c), False
+    if (s0 == 1 or r == 1) and (s1 >= r or c == 1):
+        return t, max(s1, r), True
+    return t.contiguous(), c, False
+
+
+def _mm_f32(Al, Bl, out=None, bias=None, relu=False):
+    """out = Al @ Bl (logical [M,K] x [K,N]) through one gemm_f32 launch;
+    either operand may be a transposed or column-sliced view.  `out` is a
+    [M,N] view with unit column stride (overwritten)."""
+    M, K = Al.shape
+    N = Bl.shape[1]
+    a, lda, ta = _mat_f32(Al)
+    b, ldb, tb = _mat_f32(Bl)
+    sk = _splitk_f32(M, N, K)
+    if out is None:
+        out = (torch.zeros if sk > 1 else torch.empty)(
+            (M, N), dtype=torch.float32, device=Al.device)
+    elif sk > 1:
+        out.zero_()
+    assert out.stride(1) == 1 or N == 1
+    ldc = max(out.stride(0), N)
+    # gemm's untransposed B is [N,K]: a row-major logical [K,N] is trans_b
+    gemm_f32(a, b, out, bias, M, N, K, lda, ldb, ldc, ta, not tb, sk,
+             relu and sk == 1)
+    if relu and sk > 1:
+        out.relu_()
+    return out
+
+
+def _bias_f32(b):
+    return None if b is None else b.float().contiguous()
+
+
+def fc_forward_f32(x, w, b, relu=False):
+    if x.dtype != torch.float32:     # the f32 MFMA serves fp32 only
+        return reference.fc_forward(x, w, b, relu=relu)
+    return _mm_f32(x, w.float().t(), bias=_bias_f32(b), relu=relu)
+
+
+def fc_backward_f32(x, w, dy, need_dx=True, bias=True, dw_out=None,
+                    db_out=None):
+    if x.dtype != torch.float32:
+        return reference.fc_backward(x, w, dy, need_dx=need_dx, bias=bias,
+                                     dw_out=dw_out, db_out=db_out)
+    Nout, K = w.shape
+    dx = _mm_f32(dy, w.float()) if need_dx else None
+    direct = dw_out is not None and dw_out.dtype == torch.float32 \
+        and dw_out.is_contiguous() and tuple(dw_out.shape) == (Nout, K)
+    dw = _mm_f32(dy.t(), x, out=dw_out if direct else None)
+    if dw_out is not None and not direct:
+        dw_out.copy_(dw)
+        dw = dw_out
+    db = dy.sum(dim=0) if bias else None
+    return dx, dw, db
+
+
+def _rows_cl(t):
+    """[N,C,H,W] (channels-last memory) as its [N*H*W, C] row matrix."""
+    n, c, h, w = t.shape
+    return t.permute(0, 2, 3, 1).reshape(n * h * w, c)
+
+
+def _conv_geom_f32(x, w, stride, pad, dilation):
+    N, C, H, W = x.shape
+    Kout, Cg, R, S = w.shape
+    sh, sw = stride
+    ph, pw = pad
+    dh, dw = dilation
+    P = _conv_out_dim(H, R, sh, ph, dh)
+    Q = _conv_out_dim(W, S, sw, pw, dw)
+    # a 1x1 / stride 1 / unpadded conv reads the channels-last input as
+    # its own col matrix
+    direct = (R, S, sh, sw, ph, pw) == (1, 1, 1, 1, 0, 0)
+    return N, C, H, W, Kout, Cg, R, S, P, Q, direct, \
+        (P, Q, R, S, sh, sw, ph, pw, dh, dw)
+
+
+def _w_rsc_f32(w):
+    """[Kout,Cg,R,S] weights as the [Kout, R*S*Cg] GEMM operand matching
+    the col matrix's (r, s, c) k order (a view when R == S == 1)."""
+    Kout, Cg, R, S = w.shape
+    return w.float().permute(0, 2, 3, 1).reshape(Kout, R * S * Cg)
+
+
+def _col_key_f32(x, geom, groups):
+    """What a cached col matrix was gathered from: the same storage at
+    the same in-place version, and the same geometry."""
+    return (x.data_ptr(), x._version, tuple(x.shape), tuple(x.stride()),
+            geom, groups)
+
+
+def conv2d_forward_f32(x, w, b, stride, pad, dilation, groups, ctx=None,
+                       relu=False):
+    """Per group ONE GEMM: y[N*P*Q, Kg] = col[N*P*Q, R*S*Cg] · w_gᵀ, written
+    straight into the channels-last output (logical NCHW)."""
+    if x.dtype != torch.float32:
+        return reference.conv2d_forward(x, w, b, stride, pad, dilation,
+                                        groups, ctx=ctx, relu=relu)
+    N, C, H, W, Kout, Cg, R, S, P, Q, direct, geom = _conv_geom_f32(
+        x, w, stride, pad, dilation)
+    Kg = Kout // groups
+    w2 = _w_rsc_f32(w)
+    bias_f = _bias_f32(b)
+    y = torch.empty((N, Kout, P, Q), dtype=torch.float32, device=x.device,
+                    memory_format=torch.channels_last)
+    y2 = y.permute(0, 2, 3, 1).view(N * P * Q, Kout)
+    xl = _cl(x)
+    if direct:
+        x2 = _rows_cl(xl)
+    else:
+        # with a context the backward pass reuses the col matrices (one per
+        # group) instead of gathering them again; without one a single
+        # buffer serves every group in turn
+        keep = ctx is not None
+        cols = torch.empty((groups if keep else 1, N * P * Q, Cg * R * S),
+                           dtype=torch.float32, device=x.device)
+        if keep:
+            ctx["col_f32"] = (cols, _col_key_f32(x, geom, groups))
+    for g in range(groups):
+        if direct:
+            a = x2[:, g * Cg:(g + 1) * Cg]
+        else:
+            a = cols[g if keep else 0]
+            _ext.im2col_f32(xl, a, *geom, g * Cg, Cg)
+        ks = slice(g * Kg, (g + 1) * Kg)
+        _mm_f32(a, w2[ks].t(), out=y2[:, ks],
+                bias=None if bias_f is None else bias_f[ks], relu=relu)
+    return y
+
+
+def conv2d_backward_f32(x, w, dy, stride, pad, dilation, groups,
+                        need_dx=True, need_dw=True, bias=True, ctx=None,
+                        dw_out=None, db_out=None, dx_into=None):
+    """Per group: dw_g = dy_gᵀ · col and dcol = dy_g · w_g (one GEMM each),
+    then the gather-form col2im folds dcol into dx.  `ctx`, when it is the
+    forward's, supplies the col matrices.  db_out / dx_into are ignored,
+    as in the reference."""
+    if x.dtype != torch.float32:
+        return reference.conv2d_backward(
+            x, w, dy, stride, pad, dilation, groups, need_dx=need_dx,
+            need_dw=need_dw, bias=bias, ctx=ctx, dw_out=dw_out,
+            db_out=db_out, dx_into=dx_into)
+    N, C, H, W, Kout, Cg, R, S, P, Q, direct, geom = _conv_geom_f32(
+        x, w, stride, pad, dilation)
+    Kg = Kout // groups
+    kdim = Cg * R * S
+    w2 = _w_rsc_f32(w)
+    dy2 = _rows_cl(dy.contiguous(memory_format=torch.channels_last))
+    dx = dw = db = None
+    if need_dw:
+        # the GEMM yields dw in (r, s, c) order: a 1x1 kernel's is the
+        # final layout and may land in dw_out directly
+        to_arena = R == 1 and S == 1 and dw_out is not None \
+            and dw_out.dtype == torch.float32 \
+            and dw_out.is_contiguous() and dw_out.shape == w.shape
+        dw = dw_out if to_arena else torch.empty(
+            (Kout, R, S, Cg), dtype=torch.float32, device=x.device)
+        dw2 = dw.view(Kout, kdim)
+    if need_dx:
+        dx = torch.empty((N, C, H, W), dtype=torch.float32, device=x.device,
+                         memory_format=torch.channels_last)
+    xl = _cl(x)
+    if direct:
+        x2 = _rows_cl(xl)
+        if need_dx:
+            dx2 = dx.permute(0, 2, 3, 1).view(N * H * W, C)
+    else:
+        # the forward's col matrices, if its context still describes this
+        # x; popped because dcol overwrites them below
+        cols, key = ctx.pop("col_f32", (None, None)) \
+            if isinstance(ctx, dict) else (None, None)
+        cached = cols is not None and key == _col_key_f32(x, geom, groups)
+        if not cached:
+            cols = torch.empty((1, N * P * Q, kdim), dtype=torch.float32,
+                               device=x.device)
+    for g in range(groups):
+        ks = slice(g * Kg, (g + 1) * Kg)
+        cs = slice(g * Cg, (g + 1) * Cg)
+        if not direct:
+            col = cols[g if cached else 0]
+        if need_dw:
+            if direct:
+                a = x2[:, cs]
+            else:
+                if not cached:
+                    _ext.im2col_f32(xl, col, *geom, g * Cg, Cg)
+                a = col
+            _mm_f32(dy2[:, ks].t(), a, out=dw2[ks])
+        if need_dx:
+            if direct:
+                _mm_f32(dy2[:, ks], w2[ks], out=dx2[:, cs])
+            else:
+                _mm_f32(dy2[:, ks], w2[ks], out=col)
+                _ext.col2im_f32(col, dx, *geom, g * Cg, Cg)
+    if need_dw and dw is not dw_out:
+        dw = dw.permute(0, 3, 1, 2)          # back to [Kout,Cg,R,S]
+        if dw_out is not None:
+            dw_out.copy_(dw)
+            dw = dw_out
+        else:
+            dw = dw.contiguous()
+    if bias:
+        db = dy.sum(dim=(0, 2, 3))
+    return dx, dw, db
+
+
 # ------------------------------------------------------------- activations
 
 def relu_forward(x, negative_slope=0.0):

@@ -143,6 +143,9 @@ __global__ void dropout_fwd_kernel(const u16* __restrict__ x,
                                    const unsigned long long* __restrict__ seedp,
                                    int64_t n) {
   uint64_t seed = *seedp;
+  // scale y by the mask AS STORED (bf16): backward is dx = dy * mask, and
+  // a forward scaled by the unrounded 1/keep would disagree with it
+  inv_keep = bf2f(f2bf(inv_keep));
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
        i < n; i += (int64_t)gridDim.x * blockDim.x) {
     float u = (hash_rng(seed, i) >> 8) * (1.f / 16777216.f);

@@ -32,10 +32,10 @@ void gemm_conv_fwd(const void* X, const void* B, void* C,
                    const float* bias, const void* zpage, int M, int N,
                    int K, int ldb, int ldc, bool relu, bool accum,
                    const int* geom, hipStream_t stream);
-void gemm_conv_dw(const void* A, const void* X, float* C, int M, int N,
-                  int K, int lda, int ldc, int store_mode, int splitk,
-                  float alpha, float* db, const int* geom,
-                  hipStream_t stream);
+void gemm_conv_dw(const void* A, const void* X, float* C,
+                  const void* zpage, int M, int N, int K, int lda, int ldc,
+                  int store_mode, int splitk, float alpha, float* db,
+                  const int* geom, hipStream_t stream);
 void gemm_conv_fwd_sc(const void* X, const void* B, void* C,
                       const float* bias, int M, int N, int K, int ldb,
                       int ldc, bool relu, const int* geom,
@@ -44,7 +44,6 @@ void gemm_conv_dw_sc(const void* A, const void* X, float* C, int M,
                      int N, int K, int lda, int ldc, int store_mode,
                      int splitk, float alpha, float* db, const int* geom,
                      hipStream_t stream);
-void tr16_probe(float* out, int mode, hipStream_t stream);
 void repack_weights(const int64_t* table, int ndesc, int64_t max_total,
                     hipStream_t stream);
 void dw_unpack_acc(const float* dwp, float* arena, int Kout, int Cg,
@@ -320,11 +319,14 @@ void py_gemm_conv_fwd(Tensor X, Tensor B, Tensor C,
 }
 
 void py_gemm_conv_dw(Tensor A, Tensor X, Tensor C,
-                     c10::optional<Tensor> db, int64_t M, int64_t N,
+                     c10::optional<Tensor> db, Tensor zpage, int64_t M,
+                     int64_t N,
                      int64_t K, int64_t lda, int64_t ldc,
                      int64_t store_mode, int64_t splitk, double alpha,
                      std::vector<int64_t> geom) {
   CHECK_CUDA(A); CHECK_BF16(A); CHECK_BF16(X); CHECK_F32(C);
+  CHECK_CUDA(zpage); CHECK_BF16(zpage);
+  TORCH_CHECK(zpage.numel() >= 8, "zpage must hold 16 zero bytes");
   float* dbp = nullptr;
   if (db.has_value()) {
     CHECK_F32(db.value());
@@ -334,7 +336,7 @@ void py_gemm_conv_dw(Tensor A, Tensor X, Tensor C,
   TORCH_CHECK(geom.size() == 14, "geom must have 14 ints");
   for (int i = 0; i < 14; ++i) g[i] = (int)geom[i];
   cosamd::gemm_conv_dw(A.data_ptr(), X.data_ptr(), C.data_ptr<float>(),
-                       (int)M, (int)N, (int)K, (int)lda, (int)ldc,
+                       zpage.data_ptr(), (int)M, (int)N, (int)K, (int)lda, (int)ldc,
                        (int)store_mode, (int)splitk, (float)alpha, dbp,
                        g, cur_stream());
 }
@@ -673,10 +675,6 @@ int64_t py_lstm_persist_bwd(Tensor dy, Tensor w_hcT, Tensor cont,
       cur_stream());
 }
 
-void py_tr16_probe(Tensor out, int64_t mode) {
-  cosamd::tr16_probe(out.data_ptr<float>(), (int)mode, cur_stream());
-}
-
 void py_transpose(Tensor in, Tensor out, int64_t R, int64_t C) {
   CHECK_BF16(in); CHECK_BF16(out);
   cosamd::transpose_bf16(in.data_ptr(), out.data_ptr(), R, C, cur_stream());
@@ -853,7 +851,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam_update_multi", &py_adam_update_multi);
   m.def("colsum", &py_colsum);
   m.def("transpose", &py_transpose);
-  m.def("tr16_probe", &py_tr16_probe);
   m.def("repack_weights", &py_repack_weights);
   m.def("dw_unpack_acc", &py_dw_unpack_acc);
   m.def("s2d_pack", &py_s2d_pack);

@@ -15,6 +15,8 @@
 //   stage_*          global -> LDS; the only part that differs per operand
 //   load_frags_mfma  LDS -> fragments -> 16x16x32 bf16 MFMA (fp32 acc)
 //   pipelined_loop   counted-vmcnt K loop for the DMA-staged kernels
+//                    (gemm_conv_dw_tr_kernel has its own [k][col] image,
+//                    transposed fragment reads and ring; see there)
 //   epilogue_bf16    bias + ReLU + alpha, bf16 store or RMW accumulate
 //   epilogue_f32     fp32 plain store or atomic add (split-K)
 //
@@ -32,8 +34,17 @@
 //   gemm_wide_tt_kernel<STORE, BStage>           launch_wide_tt
 //     128x256 tile, 8 waves, trans/trans weight gradients with optional
 //     fused db.  BStage = BGuarded (TT branch of gemm_bf16_batched),
-//     BImplicit (gemm_conv_dw), BImplicitSC (gemm_conv_dw_sc); each with
-//     STORE 1 (single split, plain store) or 2 (split-K atomics).
+//     BImplicit (gemm_conv_dw's fallback), BImplicitSC (gemm_conv_dw_sc);
+//     each with STORE 1 (single split, plain store) or 2 (split-K
+//     atomics).  Both operands staged through registers (u32 k-pair
+//     ds_write scatter), one LDS buffer, two barriers per tile.
+//   gemm_conv_dw_tr_kernel<STORE, DEPTH>         gemm_conv_dw
+//     same tile, contract and epilogue as gemm_wide_tt_kernel<., BImplicit>
+//     without db; both operands DMA-staged in their K-major layout into a
+//     DEPTH-stage ring (counted vmcnt, one barrier per tile), fragments by
+//     ds_read_b64_tr_b16.  Taken when db == nullptr and every 16-byte
+//     source chunk is aligned and whole (M, lda, C, c0, Cg, Kcol % 8 == 0,
+//     A and X 16-byte aligned); COS_DW_TR=0 forces the fallback.
 // w8 (use_w8): 8-wave blocks when M or N <= 256, forced by COS_GEMM_W8.
 //
 // Replaces the reference's cuBLAS calls inside conv/ip layers (SURVEY.md
@@ -878,30 +889,228 @@ __global__ __launch_bounds__(WAVES * 64, 2) void gemm_conv_fwd_sc_kernel(
                            wm, wn, lane, relu, 1.f, std::false_type{});
 }
 
-// ---- tr16 semantics probe: fills LDS with elem index, every lane does
-// one ds_read_b64_tr_b16 at its own address and dumps v[0..3] — verifies
-// the (addr + j*16) element pattern on hardware.
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+// ------------------------------------- DMA-staged conv dW (trans/trans)
+// gemm_wide_tt_kernel<., BImplicit> with both operands staged by
+// direct-to-LDS DMA in their natural K-major layout and transposed on
+// the way out of LDS by ds_read_b64_tr_b16: no staging registers, no
+// ds_write scatter, and a counted-vmcnt ring instead of two full drains
+// per tile.
+//
+// LDS image of one K tile (one ring stage, 24 KB): three [32 k][128 col]
+// bf16 sub-images of 256-byte rows — A (dy, 128 m), then the two
+// 128-column halves of the 256-wide col tile.  Within a sub-image the
+// sixteen 16-byte chunks of a row are XOR-swizzled (dw_tr_off below;
+// tests/test_conv_dw_tr_layout.py mirrors it and checks bijection,
+// fragment contents and bank conflicts).  DMA writes LDS linearly, so
+// the swizzle sits on the SOURCE side as in stage_direct_fast: the lane
+// filling chunk position (row, ch') fetches global chunk ch' ^ f(row).
+//
+// Fragment read: per 16-lane group g = lane>>4 a transposed read takes a
+// block of 4 k-rows x 16 columns; lane 4q+p supplies the address of row
+// q, columns 4p..4p+3, and lane i receives column i.  Two reads (k-rows
+// 8g..8g+3 and 8g+4..8g+7 at columns c0..c0+15) hand lane (i, g) the 8
+// consecutive k of row c0+i: the 16x16x32 operand load_frags_mfma builds
+// from one ds_read_b128.  Needs EXEC all ones (no divergence around the
+// reads) and 8-byte-aligned addresses.
 
-__global__ void tr16_probe_kernel(float* out, int mode) {
-  __shared__ bf16 lds[2048];
-  for (int i = threadIdx.x; i < 2048; i += blockDim.x)
-    lds[i] = f2bf((float)i);
-  __syncthreads();
-  int lane = threadIdx.x & 63;
-  int base;
-  if (mode == 0) base = lane;                       // low bits sweep
-  else if (mode == 1) base = lane * 16;             // tile sweep
-  else if (mode == 2) base = (lane & 3) + (lane >> 2) * 16;  // quad cols
-  else base = (lane & 15) + (lane >> 4) * 128;      // frag pattern
-  auto* p = (__attribute__((address_space(3))) bf16x4*)(lds + base);
-  bf16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) out[lane * 4 + j] = bf2f(v[j]);
+constexpr int TR_SUB = 32 * 256;          // bytes of one [32][128] image
+constexpr int TR_STAGE = 3 * TR_SUB;      // A + two B halves
+// Ring depth 3 (72 KB, two blocks per CU).  Measured on the five AlexNet
+// dW shapes at the default split (profiles/alexnet_1gpu_dw_tr.md): depth
+// 2, 3 and 4 are within 2% of each other there; 4 (96 KB, one block per
+// CU) is 9-27% slower once the grid exceeds one block per CU.
+constexpr int DW_TR_DEPTH = 3;
+
+// byte offset of 16-byte chunk ch (0..15) of k-row `row` (0..31) inside
+// a [32][128] sub-image.  Mirrored by dw_tr_off in
+// tests/test_conv_dw_tr_layout.py — change both together.
+__device__ __forceinline__ int dw_tr_off(int row, int ch) {
+  return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
 }
 
-void tr16_probe(float* out, int mode, hipStream_t stream) {
-  tr16_probe_kernel<<<1, 64, 0, stream>>>(out, mode);
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+
+// One transposed read, as inline assembly rather than
+// __builtin_amdgcn_ds_read_tr16_b64_v4bf16: the compiler cannot tell an
+// LDS read of one ring stage from the DMA in flight into another, so
+// before every LDS read it can see it drains vmcnt to 0 — which would
+// wait for the tiles just prefetched and undo the ring.  Reads it cannot
+// see get no such wait; wait_frags_tr supplies the lgkmcnt wait they need.
+__device__ __forceinline__ bf16x4 ds_read_tr16(unsigned addr) {
+  bf16x4 v;
+  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr) : "memory");
+  return v;
+}
+
+// all of a tile's transposed reads have landed; the operands tie the
+// wait to the registers so no consumer is scheduled above it
+__device__ __forceinline__ void wait_frags_tr(bf16x4 (&a)[4][2],
+                                              bf16x4 (&b)[4][2]) {
+  asm volatile("s_waitcnt lgkmcnt(0)"
+               : "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[1][0]), "+v"(a[1][1]),
+                 "+v"(a[2][0]), "+v"(a[2][1]), "+v"(a[3][0]), "+v"(a[3][1]),
+                 "+v"(b[0][0]), "+v"(b[0][1]), "+v"(b[1][0]), "+v"(b[1][1]),
+                 "+v"(b[2][0]), "+v"(b[2][1]), "+v"(b[3][0]), "+v"(b[3][1])
+               :: "memory");
+}
+
+// Sibling of pipelined_loop rather than a generalisation of it: here the
+// DMA of tile t+DEPTH-1 is issued AFTER barrier t (into the slot tile t-1
+// was read from), which gives DEPTH-1 tiles of prefetch on one barrier
+// per tile at any depth, and every DMA always issues — tiles past the
+// split's end fetch the zero page — so the counted wait is exact for any
+// tile count >= 1 (pipelined_loop needs >= 2 and a power-of-two ring).
+template <int STORE, int DEPTH>
+__global__ __launch_bounds__(WNT, DEPTH <= 3 ? 4 : 2)
+void gemm_conv_dw_tr_kernel(
+    const bf16* __restrict__ A, const bf16* __restrict__ X,
+    const bf16* __restrict__ zpage, float* __restrict__ C, int M, int N,
+    int K, int lda, int ldc, int ksplit, float alpha, CGeom gm) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[DEPTH * TR_STAGE];
+
+  Tile t = decode_tile<WBN>(M, N);
+  int tile_m = t.tile_m, tile_n = t.tile_n;
+  int k_begin = blockIdx.y * ksplit;
+  int k_end = min(K, k_begin + ksplit);
+
+  int tid = threadIdx.x;
+  int wave = tid >> 6, lane = tid & 63;
+  int wm = wave >> 2, wn = wave & 3;     // 2x4 wave grid, 64x64 each
+
+  // ---- staging: wave w's DMA fills bytes [1024w, 1024w+1024) of each
+  // sub-image, i.e. k-rows 4w..4w+3; lane l fills chunk position
+  // (4w + l/16, l%16) and so fetches source chunk sch of that k-row.
+  // Everything but the output pixel (the k-row) is fixed per lane.
+  int srow = wave * 4 + (lane >> 4);
+  int sch = (dw_tr_off(srow, lane & 15) >> 4) & 15;
+  int am = tile_m + sch * 8;             // A column octet (M % 8 == 0)
+  bool a_ok = am < M;
+  int hr[2], ws[2], cc[2];
+  bool col_ok[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    int gr = tile_n + j * 128 + sch * 8;  // col-matrix column octet
+    unsigned rs = mdiv(gr, gm.mCg);
+    int c = gr - rs * gm.Cg;
+    unsigned r = mdiv(rs, gm.mS);
+    int s = rs - r * gm.S;
+    col_ok[j] = gr < gm.Kcol;            // octet fully in/out (Kcol%8==0)
+    hr[j] = (int)r * gm.dil - gm.ph;
+    ws[j] = s * gm.dil - gm.pw;
+    cc[j] = gm.c0 + c;
+  }
+  const unsigned short* xs = reinterpret_cast<const unsigned short*>(X);
+  const unsigned short* as = reinterpret_cast<const unsigned short*>(A);
+  typedef const __attribute__((address_space(1))) unsigned int* gptr;
+  typedef __attribute__((address_space(3))) unsigned int* lptr;
+
+  // Branch-free: every lane computes its address and then selects it or
+  // the zero page, so each DMA issues once with EXEC all ones.  (Left to
+  // itself the compiler branches around the 64-bit address arithmetic
+  // and issues the DMA once per side of the branch; keep_v pins the
+  // computed offset in front of the select.)
+  auto keep_v = [](int64_t v) {
+    asm volatile("" : "+v"(v));
+    return v;
+  };
+  auto stage = [&](int slot, int k0) {
+    unsigned char* base = smem + slot * TR_STAGE + wave * 1024;
+    int k = k0 + srow;                   // output pixel (npq) index
+    bool k_ok = k < k_end;
+    int64_t aoff = keep_v((int64_t)k * lda + am);
+    const void* asrc = (k_ok & a_ok) ? (const void*)(as + aoff)
+                                      : (const void*)zpage;
+    __builtin_amdgcn_global_load_lds((gptr)asrc, (lptr)base, 16, 0, 0);
+    unsigned n = mdiv(k, gm.mPQ);
+    unsigned pq = k - n * gm.PQ;
+    unsigned p = mdiv(pq, gm.mQ);
+    unsigned q = pq - p * gm.Q;
+    int nH = (int)n * gm.H, ph0 = (int)p * gm.sh, qw0 = (int)q * gm.sw;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      int hi = ph0 + hr[j], wi = qw0 + ws[j];
+      // unsigned compares fold the >= 0 tests; & not &&: no branches
+      bool ok = k_ok & col_ok[j] & ((unsigned)hi < (unsigned)gm.H) &
+                ((unsigned)wi < (unsigned)gm.W);
+      // pixel index in 32 bits (the magic division already needs
+      // NPQ < 2^20, and NHW is about stride^2 times that), element
+      // offset in 64
+      int64_t boff = keep_v((int64_t)((nH + hi) * gm.W + wi) * gm.C + cc[j]);
+      const void* bsrc = ok ? (const void*)(xs + boff) : (const void*)zpage;
+      __builtin_amdgcn_global_load_lds(
+          (gptr)bsrc, (lptr)(base + (1 + j) * TR_SUB), 16, 0, 0);
+    }
+  };
+
+  // ---- fragment read addresses (fixed per lane): group g reads k-rows
+  // 8g+4h+q; lane 4q+p of the group supplies columns 4p..4p+3, i.e.
+  // 8-byte half p&1 of chunk c0 + p/2 — addressed through dw_tr_off
+  // because the XOR can swap the two chunks of a row's 32 bytes.
+  // Fragment f's chunk is c0 + 2f with bits 1-2 of c0 clear, and the
+  // swizzle is an XOR too, so its address is fragment 0's ^ (f << 5):
+  // four address registers instead of sixteen.
+  int fq = (lane >> 2) & 3, fp = lane & 3, fg = lane >> 4;
+  int a_addr[2], b_addr[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    int row = 8 * fg + 4 * h + fq;
+    a_addr[h] = dw_tr_off(row, wm * 8 + (fp >> 1)) + 8 * (fp & 1);
+    b_addr[h] = (1 + (wn >> 1)) * TR_SUB +
+                dw_tr_off(row, (wn & 1) * 8 + (fp >> 1)) + 8 * (fp & 1);
+  }
+
+  unsigned lds0 = (unsigned)(uintptr_t)(
+      (__attribute__((address_space(3))) unsigned char*)smem);
+
+  f32x4 acc[4][4] = {};
+
+  constexpr int PF = DEPTH - 1;          // tiles in flight ahead
+  constexpr int VMCNT = 3 * (PF - 1);    // 3 DMAs per wave per tile
+  int tiles = (k_end - k_begin + BK - 1) / BK;
+#pragma unroll
+  for (int p = 0; p < PF; ++p) stage(p, k_begin + p * BK);
+  int cur = 0;                           // ring slot of tile i
+  for (int i = 0; i < tiles; ++i) {
+    wait_vmcnt<VMCNT>();                 // this wave's part of tile i landed
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();        // everyone's did; tile i-1 is read
+    int nxt = cur == 0 ? DEPTH - 1 : cur - 1;   // (i + PF) % DEPTH
+    stage(nxt, k_begin + (i + PF) * BK);
+    int img = cur * TR_STAGE;            // multiple of 128: keeps the XOR
+    bf16x4 ar[4][2], br[4][2];
+#pragma unroll
+    for (int f = 0; f < 4; ++f)
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        br[f][h] = ds_read_tr16(lds0 + ((img + b_addr[h]) ^ (f << 5)));
+#pragma unroll
+    for (int f = 0; f < 4; ++f)
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        ar[f][h] = ds_read_tr16(lds0 + ((img + a_addr[h]) ^ (f << 5)));
+    wait_frags_tr(ar, br);
+    bf16x8 afrag[4], bfrag[4];
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+      afrag[f] = __builtin_shufflevector(ar[f][0], ar[f][1], 0, 1, 2, 3, 4,
+                                         5, 6, 7);
+      bfrag[f] = __builtin_shufflevector(br[f][0], br[f][1], 0, 1, 2, 3, 4,
+                                         5, 6, 7);
+    }
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int fm = 0; fm < 4; ++fm)
+#pragma unroll
+      for (int fn = 0; fn < 4; ++fn)
+        acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            afrag[fm], bfrag[fn], acc[fm][fn], 0, 0, 0);
+    __builtin_amdgcn_s_setprio(0);
+    cur = cur + 1 == DEPTH ? 0 : cur + 1;
+  }
+  wait_vmcnt<0>();                       // the zero-page tail DMAs
+
+  epilogue_f32<STORE, false, 4, 64>(acc, C, nullptr, M, N, ldc, tile_m,
+                                    tile_n, wm, wn, lane, 0, alpha);
 }
 
 // ------------------------------------------------------------------- host
@@ -1075,13 +1284,36 @@ void gemm_conv_dw_sc(const void* A, const void* X, float* C, int M,
                  BImplicitSC{(const bf16*)X, make_geom(geom)}, stream);
 }
 
-void gemm_conv_dw(const void* A, const void* X, float* C, int M, int N,
-                  int K, int lda, int ldc, int store_mode, int splitk,
-                  float alpha, float* db, const int* geom,
-                  hipStream_t stream) {
-  launch_wide_tt((const bf16*)A, C, M, N, K, lda, ldc, store_mode,
-                 split_k(K, splitk), alpha, db,
-                 BImplicit{(const bf16*)X, make_geom(geom)}, stream);
+// The DMA-staged kernel needs every 16-byte source chunk aligned and
+// wholly inside or outside its operand; anything else, and a fused db,
+// runs the register-staged kernel.  COS_DW_TR=0 forces the latter (A/B).
+void gemm_conv_dw(const void* A, const void* X, float* C,
+                  const void* zpage, int M, int N, int K, int lda, int ldc,
+                  int store_mode, int splitk, float alpha, float* db,
+                  const int* geom, hipStream_t stream) {
+  // read per call, not cached: the tests flip it inside one process
+  const char* tr_e = getenv("COS_DW_TR");
+  bool tr_env = !(tr_e && tr_e[0] == '0');
+  CGeom gm = make_geom(geom);
+  SplitK sk = split_k(K, splitk);
+  bool tr = tr_env && db == nullptr && zpage != nullptr &&
+            ((M | lda | gm.C | gm.c0 | gm.Cg | gm.Kcol) % 8 == 0) &&
+            (((uintptr_t)A | (uintptr_t)X) % 16 == 0);
+  if (!tr) {
+    launch_wide_tt((const bf16*)A, C, M, N, K, lda, ldc, store_mode, sk,
+                   alpha, db, BImplicit{(const bf16*)X, gm}, stream);
+    return;
+  }
+  int mblocks = (M + BM - 1) / BM, nblocks = (N + WBN - 1) / WBN;
+  dim3 grid(mblocks * nblocks, sk.zblocks);
+  if (store_mode == 1 && sk.zblocks == 1)
+    gemm_conv_dw_tr_kernel<1, DW_TR_DEPTH><<<grid, WNT, 0, stream>>>(
+        (const bf16*)A, (const bf16*)X, (const bf16*)zpage, C, M, N, K, lda,
+        ldc, sk.ksplit, alpha, gm);
+  else
+    gemm_conv_dw_tr_kernel<2, DW_TR_DEPTH><<<grid, WNT, 0, stream>>>(
+        (const bf16*)A, (const bf16*)X, (const bf16*)zpage, C, M, N, K, lda,
+        ldc, sk.ksplit, alpha, gm);
 }
 
 void gemm_bf16(const void* A_, const void* B_, void* C, const float* bias,

@@ -72,7 +72,7 @@ def _splitk_for(mb: int, nb: int, K: int) -> int:
     return max(1, min(K // 256, target // max(1, tiles)))
 
 
-def _splitk_tt(M: int, N: int, K: int) -> int:
+def _splitk_tt(M: int, N: int, K: int, default: int = 448) -> int:
     """Split-K for the fused trans/trans GEMMs: the wide kernel re-tiles
     N to 256, and the sweep (scratch/sweep_tt_sk.py, MI355X) shows the
     optimum at ~448 8-wave blocks with >=512 K per block."""
@@ -80,8 +80,19 @@ def _splitk_tt(M: int, N: int, K: int) -> int:
     nb = (N + 255) // 256 if N > 128 else (N + 127) // 128
     if K < 1024:
         return 1
-    target = int(os.environ.get("COS_SPLITK_TARGET", "448"))
+    target = int(os.environ.get("COS_SPLITK_TARGET", default))
     return max(1, min(target // max(1, mb * nb), K // 512))
+
+
+def _splitk_dw(M: int, N: int, K: int, implicit: bool) -> int:
+    """Split-K for the conv dW GEMM.  The DMA-staged kernel
+    (gemm_conv_dw_tr_kernel, the implicit Cg % 8 == 0 route) is fastest
+    at one block per CU in a single wave of blocks — 256 — on all five
+    AlexNet shapes (profiles/alexnet_1gpu_dw_tr.md); the register-staged
+    kernel keeps its 448."""
+    tr = implicit and os.environ.get("COS_DW_TR", "1") != "0" and \
+        not bool(int(os.environ.get("COS_FUSE_DB", "0")))
+    return _splitk_tt(M, N, K, 256 if tr else 448)
 
 
 def _pad128(n: int) -> int:
@@ -553,7 +564,8 @@ def _conv_dw_s2d(ctx, dyg, ld_dy, dw_out):
     st, Rp, Sp, Cp, Hp, Wp, Kcol_s, Kpad_s = ctx["s2d"]
     Kout, NPQ = Kg, N * P * Q
     xs = ctx["xs2d"]
-    sk_tt = _splitk_tt(Kout, Kpad_s, NPQ)
+    sk_tt = _splitk_dw(Kout, Kpad_s, NPQ,
+                       (Cp | Kout | ld_dy | Kcol_s) % 8 == 0)
     if sk_tt == 1:
         dwp = torch.empty((Kout, Kpad_s), dtype=torch.float32,
                           device=xs.device)
@@ -562,8 +574,8 @@ def _conv_dw_s2d(ctx, dyg, ld_dy, dw_out):
         dwp = _scratch_buf((Kout, Kpad_s), torch.float32, xs.device)
         store_dw = 2
     geom = [Hp, Wp, Cp, P, Q, 1, 1, 0, 0, 1, Sp, 0, Cp, Kcol_s]
-    _ext.gemm_conv_dw(dyg, xs, dwp, None, Kout, Kpad_s, NPQ, ld_dy,
-                      Kpad_s, store_dw, sk_tt, 1.0, geom)
+    _ext.gemm_conv_dw(dyg, xs, dwp, None, _zpage(xs.device), Kout, Kpad_s,
+                      NPQ, ld_dy, Kpad_s, store_dw, sk_tt, 1.0, geom)
     if dw_out is not None and dw_out.dtype == torch.float32 \
             and dw_out.is_contiguous() \
             and tuple(dw_out.shape) == (Kout, C, R, S):
@@ -673,7 +685,8 @@ def conv2d_backward(x, w, dy, stride, pad, dilation, groups,
         # fused trans/trans dw (u32 k-pair staged; round 2): reads dy2/col
         # exactly once instead of transpose kernels + an extra HBM pass
         use_tt = bool(int(os.environ.get("COS_DW_TT", "1")))
-        sk_tt = _splitk_tt(Kg, Kpad, NPQ) if use_tt else 0
+        dw_tr = dw_implicit and (C | Cg | Kg | ld_dy | Kcol) % 8 == 0
+        sk_tt = _splitk_dw(Kg, Kpad, NPQ, dw_tr) if use_tt else 0
         if use_tt and sk_tt == 1:
             # single split: every output element is written by exactly
             # one block — plain store, no zero-init pass needed
@@ -693,7 +706,8 @@ def conv2d_backward(x, w, dy, stride, pad, dilation, groups,
                 geom = [H, W, C, P, Q, sh, sw, ph, pw, dil, S, g * Cg,
                         Cg, Kcol]
                 _ext.gemm_conv_dw(_dyg(g), ctx["xl"],
-                                  dwp[g * Kg:], db_slice, Kg, Kpad, NPQ,
+                                  dwp[g * Kg:], db_slice,
+                                  _zpage(dy.device), Kg, Kpad, NPQ,
                                   ld_dy, Kpad, store_dw, sk_tt, 1.0,
                                   geom)
             elif use_tt and dw_implicit_sc:

@@ -1,5 +1,6 @@
-"""Vision layer catalog: Convolution, Pooling, LRN, InnerProduct, activations,
-Dropout, Softmax(+Loss), Accuracy, BatchNorm/Scale/Bias.
+"""Vision layer catalog: Convolution, Deconvolution, Pooling, LRN,
+InnerProduct, activations, Dropout, Softmax(+Loss), Accuracy,
+BatchNorm/Scale/Bias.
 
 Semantics match upstream Caffe (reference layer census: SURVEY.md §2.5 row
 "Layer catalog", §3.6 kernel table).  All math dispatches through
@@ -115,6 +116,71 @@ class ConvolutionLayer(Layer):
         if db is not None and db is not db_out:
             self.acc_param_diff(1, db)
         if propagate_down[0] and dx is not dx_into:
+            self.acc_blob_diff(bottom[0], dx, False)
+
+
+@register_layer("Deconvolution")
+class DeconvolutionLayer(Layer):
+    """Transposed convolution.  Reads convolution_param like Convolution;
+    the weight blob is [Cin, num_output/group, kh, kw] as in Caffe, and the
+    top is stride*(H-1) + dilation*(k-1) + 1 - 2*pad high."""
+
+    def setup(self, bottom, top):
+        p = self.param.convolution_param
+        self.num_output = int(p.num_output)
+        self.kh, self.kw = _resolve_hw(p, "kernel")
+        self.sh, self.sw = _resolve_hw(p, "stride", 1)
+        if self.sh == 0:
+            self.sh = self.sw = 1
+        self.ph, self.pw = _resolve_hw(p, "pad", 0)
+        dil = p.dilation
+        self.dil = int(dil[0]) if dil else 1
+        self.groups = int(p.group)
+        self.bias_term = p.bias_term
+        cin = bottom[0].shape[1]
+        assert cin % self.groups == 0 and self.num_output % self.groups == 0
+        self.add_param([cin, self.num_output // self.groups, self.kh,
+                        self.kw], p.weight_filler, name=self.name + "_w")
+        if self.bias_term:
+            self.add_param([self.num_output], p.bias_filler,
+                           name=self.name + "_b")
+
+    def forward(self, bottom, top):
+        x = bottom[0].data
+        w = self.weight(0)
+        b = self.blobs[1].data if self.bias_term else None  # fp32 master
+        self._ctx = {}
+        top[0].data = ops.deconv2d_forward(
+            x, w, b, (self.sh, self.sw), (self.ph, self.pw),
+            (self.dil, self.dil), self.groups, ctx=self._ctx)
+        return 0.0
+
+    def backward(self, top, propagate_down, bottom):
+        dy = top[0].diff
+        x = bottom[0].data
+        w = self.weight(0)
+        need_dw = self.blobs[0]._lr_mult != 0
+        need_db = self.bias_term and self.blobs[1]._lr_mult != 0
+        wb = self.blobs[0]
+        dw_out = None
+        if need_dw and getattr(wb, "_grad_virgin", False):
+            d = wb.ensure_diff()
+            if d.dtype == torch.float32 and d.is_contiguous():
+                dw_out = d.view(wb.shape)
+        db_out = self._bias_arena() if need_db else None
+        dx, dw, db = ops.deconv2d_backward(
+            x, w, dy, (self.sh, self.sw), (self.ph, self.pw),
+            (self.dil, self.dil), self.groups,
+            need_dx=propagate_down[0], need_dw=need_dw, bias=need_db,
+            dw_out=dw_out, db_out=db_out)
+        if dw is not None:
+            if dw is dw_out:
+                wb._grad_virgin = False
+            else:
+                self.acc_param_diff(0, dw)
+        if db is not None and db is not db_out:
+            self.acc_param_diff(1, db)
+        if propagate_down[0]:
             self.acc_blob_diff(bottom[0], dx, False)
 
 

@@ -74,7 +74,8 @@ _TORCH_OK_ON_GPU = set()
 # per-config dtype policy).  Solver update ops are excluded: the fused
 # fp32-arena update kernels serve both dtypes natively.
 _FP32_REF_ON_GPU = {
-    "conv2d_forward", "conv2d_backward", "fc_forward", "fc_backward",
+    "conv2d_forward", "conv2d_backward", "deconv2d_forward",
+    "deconv2d_backward", "fc_forward", "fc_backward",
     "relu_forward", "relu_backward", "sigmoid_forward", "sigmoid_backward",
     "tanh_forward", "tanh_backward", "maxpool_forward", "maxpool_backward",
     "avgpool_forward", "avgpool_backward", "global_avgpool_forward",
@@ -174,6 +175,8 @@ def _dispatch(name: str):
 # public op surface — one callable per op, same signatures as reference.py
 conv2d_forward = _dispatch("conv2d_forward")
 conv2d_backward = _dispatch("conv2d_backward")
+deconv2d_forward = _dispatch("deconv2d_forward")
+deconv2d_backward = _dispatch("deconv2d_backward")
 fc_forward = _dispatch("fc_forward")
 fc_backward = _dispatch("fc_backward")
 relu_forward = _dispatch("relu_forward")

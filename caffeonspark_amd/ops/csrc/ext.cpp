@@ -54,6 +54,11 @@ void s2d_pack(const void* x, void* out, int N, int H, int W, int C, int st,
               int64_t sH, int64_t sW, hipStream_t stream);
 void s2d_pack_weight(const void* src, void* dst, int Kout, int Cg, int R,
                      int S, int st, int Kpad, hipStream_t stream);
+void d2s_pack_weight(const void* src, void* dst, int Ci, int Co, int R,
+                     int S, int st, int Kpad, hipStream_t stream);
+void d2s_unpack(const void* z, void* y, int N, int Co, int Ho, int Wo,
+                int st, int ph, int pw, int Hp, int Wp, int64_t sN,
+                int64_t sC, int64_t sH, int64_t sW, hipStream_t stream);
 void data_transform(const void* src, int64_t src_bytes, const int64_t* table,
                     const int64_t* table_host, int N, const float* mean,
                     int mean_mode, int64_t mean_numel, int mC, int mH,
@@ -637,6 +642,59 @@ void py_s2d_pack_weight(Tensor src, Tensor dst, int64_t Kout, int64_t Cg,
                           cur_stream());
 }
 
+// depth-to-space weight pack (d2s.hip): src is the caffe deconvolution
+// weight [Ci][Co][R][S]; dst the GEMM B operand [>= st*st*Co][Kpad], whose
+// live [st*st*Co][R'*S'*Ci] region is fully overwritten
+void py_d2s_pack_weight(Tensor src, Tensor dst, int64_t Ci, int64_t Co,
+                        int64_t R, int64_t S, int64_t st, int64_t Kpad) {
+  CHECK_CUDA(src); CHECK_BF16(src); CHECK_CUDA(dst); CHECK_BF16(dst);
+  TORCH_CHECK(st >= 2 && Ci > 0 && Co > 0 && R > 0 && S > 0 &&
+              Ci % 8 == 0 && Kpad % 8 == 0, "bad d2s weight geometry");
+  int64_t Rp = (R + st - 1) / st, Sp = (S + st - 1) / st;
+  const int64_t lim = 1ll << 31;
+  TORCH_CHECK(Ci < lim && Co < lim && R < lim && S < lim && st < lim &&
+              Kpad < lim && st * st * Co < lim && Rp * Sp * Ci < lim,
+              "d2s weight too large");
+  TORCH_CHECK(src.is_contiguous() && src.numel() == Ci * Co * R * S,
+              "bad d2s weight source");
+  TORCH_CHECK(dst.is_contiguous() && dst.dim() == 2 &&
+              dst.size(0) >= st * st * Co && dst.size(1) == Kpad &&
+              Kpad >= Rp * Sp * Ci, "bad d2s weight buffer");
+  TORCH_CHECK((uintptr_t)dst.data_ptr() % 16 == 0,
+              "d2s weight buffer must be 16-byte aligned");
+  cosamd::d2s_pack_weight(src.data_ptr(), dst.data_ptr(), (int)Ci, (int)Co,
+                          (int)R, (int)S, (int)st, (int)Kpad, cur_stream());
+}
+
+// depth-to-space unpack (d2s.hip): z is the dense GEMM output
+// [N][Hp][Wp][st*st*Co]; y any [N][Co][Ho][Wo] view, written through its
+// strides
+void py_d2s_unpack(Tensor z, Tensor y, int64_t st, int64_t ph, int64_t pw,
+                   int64_t Hp, int64_t Wp) {
+  CHECK_CUDA(z); CHECK_BF16(z); CHECK_CUDA(y); CHECK_BF16(y);
+  TORCH_CHECK(y.dim() == 4, "y must be 4-D");
+  const int64_t lim = 1ll << 31;
+  int64_t N = y.size(0), Co = y.size(1), Ho = y.size(2), Wo = y.size(3);
+  TORCH_CHECK(st >= 2 && st < lim && ph >= 0 && pw >= 0 && ph < lim &&
+              pw < lim && Hp > 0 && Wp > 0 && Hp < lim && Wp < lim,
+              "bad d2s geometry");
+  TORCH_CHECK(N < lim && Co < lim && Ho < lim && Wo < lim, "y too large");
+  TORCH_CHECK(z.is_contiguous() && z.numel() == N * Hp * Wp * st * st * Co,
+              "z must be dense [N][Hp][Wp][st*st*Co]");
+  int64_t last = 0;
+  for (int d = 0; d < 4; ++d) {
+    TORCH_CHECK(y.stride(d) >= 0, "negative stride");
+    last += (y.size(d) - 1) * y.stride(d);
+  }
+  TORCH_CHECK(y.numel() == 0 ||
+              last < (int64_t)(y.storage().nbytes() / 2) - y.storage_offset(),
+              "y view exceeds its storage");
+  cosamd::d2s_unpack(z.data_ptr(), y.data_ptr(), (int)N, (int)Co, (int)Ho,
+                     (int)Wo, (int)st, (int)ph, (int)pw, (int)Hp, (int)Wp,
+                     y.stride(0), y.stride(1), y.stride(2), y.stride(3),
+                     cur_stream());
+}
+
 void py_dw_unpack_s2d(Tensor dwp, Tensor arena, int64_t Kout, int64_t Cg,
                       int64_t R, int64_t S, int64_t st, int64_t Kpad,
                       bool accumulate) {
@@ -855,6 +913,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dw_unpack_acc", &py_dw_unpack_acc);
   m.def("s2d_pack", &py_s2d_pack);
   m.def("s2d_pack_weight", &py_s2d_pack_weight);
+  m.def("d2s_pack_weight", &py_d2s_pack_weight);
+  m.def("d2s_unpack", &py_d2s_unpack);
   m.def("data_transform", &py_data_transform);
   m.def("dw_unpack_s2d", &py_dw_unpack_s2d);
   m.def("lstm_persist_fwd", &py_lstm_persist_fwd);

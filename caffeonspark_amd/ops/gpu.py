@@ -28,6 +28,16 @@ def _pad32(k: int) -> int:
     return (k + 31) // 32 * 32
 
 
+def _kpad_dma(k: int) -> int:
+    """K extent of a GEMM run by the DMA-staged pipelined loop
+    (gemm_conv_fwd, gemm_conv_fwd_sc): whole 32-wide tiles, and at least
+    two of them — with a single tile the loop's counted wait passes before
+    the tile's DMA has landed (gemm.hip, above ADirect).  The staging
+    zero-fills k beyond the real extent and the B operand's pad columns
+    are zero, so the padding adds only zeros."""
+    return max(64, _pad32(k))
+
+
 def _cl(x: torch.Tensor) -> torch.Tensor:
     """channels_last contiguous form of a 4-D activation; the converted
     copy is cached on the tensor (keyed by torch's in-place version
@@ -247,6 +257,27 @@ def _conv_out_dim(h, k, s, p, dil):
     return (h + 2 * p - eff) // s + 1
 
 
+def _conv_implicit_ok(N, C, Cg, R, S, P, Q, imp1x1=False):
+    """Gates of the implicit-im2col forward GEMM: 8-aligned channel octets
+    (one (r,s) tap per 16-byte load), not a 1x1 kernel unless the caller
+    opted in, and the npq/k decode within the magic-divide bound."""
+    return (C % 8 == 0 and Cg % 8 == 0
+            and (not (R == S == 1) or imp1x1)
+            and N * P * Q < (1 << 20) and R * S * Cg < (1 << 20)
+            and bool(int(os.environ.get("COS_IMPLICIT", "1"))))
+
+
+def _dx_imp_ok(N, H, W, R, S, sh, sw, ph, pw, dil, Kg):
+    """Gates of the implicit data gradient beyond those of the implicit
+    forward: stride 1, 8-aligned output-channel octets, non-negative
+    flipped pads and the magic-divide bounds."""
+    return (sh == sw == 1
+            and bool(int(os.environ.get("COS_DX_IMP", "1")))
+            and Kg % 8 == 0 and dil * (R - 1) - ph >= 0
+            and dil * (S - 1) - pw >= 0 and N * H * W < (1 << 20)
+            and R * S * Kg < (1 << 20))
+
+
 def conv2d_forward(x, w, b, stride, pad, dilation, groups, ctx=None,
                    relu=False, out_into=None):
     _check_bf16(x, "conv input")
@@ -267,10 +298,7 @@ def conv2d_forward(x, w, b, stride, pad, dilation, groups, ctx=None,
     imp1x1 = (R == S == 1 and sh == sw == 1 and ph == pw == 0
               and G == 1 and C >= 256
               and bool(int(os.environ.get("COS_IMP_1X1", "0"))))
-    implicit = (C % 8 == 0 and Cg % 8 == 0
-                and (not (R == S == 1) or imp1x1)
-                and N * P * Q < (1 << 20) and R * S * Cg < (1 << 20)
-                and bool(int(os.environ.get("COS_IMPLICIT", "1"))))
+    implicit = _conv_implicit_ok(N, C, Cg, R, S, P, Q, imp1x1)
     # small-C variant (conv1-class, C%8!=0): with dil==1 / full
     # channels the k axis is CONTIGUOUS spans of the input rows, so
     # staging uses unaligned 16-byte loads straight from x (the col
@@ -297,9 +325,9 @@ def conv2d_forward(x, w, b, stride, pad, dilation, groups, ctx=None,
                                                   Cg, Kg, _pad8(Kcol),
                                                   Kcol),
                                    ctx, relu, out_into)
-    # 32-aligned K keeps every k-tile on the pipelined fast path (and
-    # bounds the implicit kernel's B reads); pad columns stay zero
-    Kpad = _pad32(Kcol) if (implicit or implicit_sc) else _pad8(Kcol)
+    # whole k-tiles, at least two, keep the pipelined fast path valid
+    # (and bound the implicit kernel's B reads); pad columns stay zero
+    Kpad = _kpad_dma(Kcol) if (implicit or implicit_sc) else _pad8(Kcol)
 
     xl = _cl(x)
     # weight repack: [K, Cg, R, S] -> bf16 [K, R, S, Cg] padded to Kpad
@@ -325,15 +353,12 @@ def conv2d_forward(x, w, b, stride, pad, dilation, groups, ctx=None,
         # gradient as ONE implicit GEMM over dy with the flipped-weight
         # layout wrF[c][(RS-1-rs)*Kout + k] (no dcol, no col2im)
         k2 = R * S * Kg
-        dx_imp = (implicit and sh == sw == 1
-                  and bool(int(os.environ.get("COS_DX_IMP", "1")))
-                  and Kg % 8 == 0 and dil * (R - 1) - ph >= 0
-                  and dil * (S - 1) - pw >= 0 and N * H * W < (1 << 20)
-                  and k2 < (1 << 20))
+        dx_imp = implicit and _dx_imp_ok(N, H, W, R, S, sh, sw, ph, pw,
+                                         dil, Kg)
         wrF = None
         k2p = 0
         if dx_imp:
-            k2p = _pad32(k2)
+            k2p = _kpad_dma(k2)
             wrF = torch.zeros((G * _pad128(Cg), k2p),
                               dtype=torch.bfloat16, device=x.device)
             w._cos_wrF = wrF
@@ -609,6 +634,49 @@ def _wino_run(xl, w, b, y, N, P, Q, C, K, relu, flip=False):
                    N, P, Q, C, K, wK, wC, ur, flip, relu)
 
 
+def _conv_dx(dyl, dyg, ld_dy, shape, wr, wrT, wrF, dx, dx_acc=False):
+    """Data gradient of the convolution `shape` describes, written into
+    dx (channels-last [N, C, H, W]); shared by conv2d_backward and the
+    Deconvolution forward pass, which IS this computation.  dyl is the
+    channels-last top gradient with row stride ld_dy and dyg(g) its
+    group-g channel slice.  With a matching flipped-weight layout wrF
+    (stride-1 convolutions, see conv2d_forward) it is one implicit GEMM
+    per group; otherwise the dcol GEMM over wr's transpose (wrT where
+    the caller has it, G == 1 only) followed by col2im."""
+    (N, C, H, W, P, Q, R, S, sh, sw, ph, pw, dil, G, Cg, Kg, Kpad,
+     Kcol) = shape
+    NPQ = N * P * Q
+    k2 = R * S * Kg
+    cgp = _pad128(Cg)
+    if wrF is not None and wrF.shape == (G * cgp, _kpad_dma(k2)) \
+            and N * H * W < (1 << 20):
+        # implicit dx: the data gradient IS a stride-1 convolution of
+        # dy with the flipped weights — one GEMM per group writes
+        # dx's NHWC alias directly (no dcol buffer, no col2im pass)
+        dx2 = dx.permute(0, 2, 3, 1).reshape(N * H * W, C)
+        for g in range(G):
+            geom = [P, Q, ld_dy, H, W, 1, 1,
+                    dil * (R - 1) - ph, dil * (S - 1) - pw, dil, S,
+                    g * Kg, Kg, k2]
+            _ext.gemm_conv_fwd(dyl, wrF[g * cgp:], dx2[:, g * Cg:],
+                               None, _zpage(dyl.device), N * H * W,
+                               Cg, _kpad_dma(k2), _kpad_dma(k2), C, False,
+                               dx_acc, geom)
+        return
+    dcol = torch.empty((NPQ, Kpad), dtype=torch.bfloat16,
+                       device=dyl.device)
+    for g in range(G):
+        # dcol[npq, kpad] = dy_g[npq, kg] @ w_g[kg, kpad]
+        wT = wrT
+        if wT is None:
+            wT = _transpose(wr[g * Kg:(g + 1) * Kg].contiguous())
+        _gemm(dyg(g), wT, dcol, None,
+              NPQ, Kpad, Kg, ld_dy, Kg, Kpad, False, False, 0, 1,
+              ma=NPQ, na=_pad128(Kpad))
+        _ext.col2im(dcol, dx, N, H, W, C, P, Q, R, S, sh, sw, ph, pw,
+                    dil, Kpad, g * Cg, Cg)
+
+
 def conv2d_backward(x, w, dy, stride, pad, dilation, groups,
                     need_dx=True, need_dw=True, bias=True, ctx=None,
                     dw_out=None, db_out=None, dx_into=None):
@@ -774,7 +842,7 @@ def conv2d_backward(x, w, dy, stride, pad, dilation, groups,
         acc_capable = not wino and (
             is_1x1 or (wrF_ is not None
                        and wrF_.shape == (G * _pad128(Cg),
-                                          _pad32(R * S * Kg))
+                                          _kpad_dma(R * S * Kg))
                        and N * H * W < (1 << 20)))
         dx_acc = acc_capable and dx_into is not None and \
             dx_into.is_contiguous(memory_format=torch.channels_last) and \
@@ -805,24 +873,6 @@ def conv2d_backward(x, w, dy, stride, pad, dilation, groups,
             _wino_run(dyl, ctx["w"], None, dx, N, H, W, Kout, C,
                       relu=False, flip=True)
             return dx, dw, db
-        wrF = getattr(ctx.get("w_ref"), "_cos_wrF", None)
-        k2 = R * S * Kg
-        cgp = _pad128(Cg)
-        if wrF is not None and wrF.shape == (G * cgp, _pad32(k2)) \
-                and N * H * W < (1 << 20):
-            # implicit dx: the data gradient IS a stride-1 convolution of
-            # dy with the flipped weights — one GEMM per group writes
-            # dx's NHWC alias directly (no dcol buffer, no col2im pass)
-            dx2 = dx.permute(0, 2, 3, 1).reshape(N * H * W, C)
-            for g in range(G):
-                geom = [P, Q, ld_dy, H, W, 1, 1,
-                        dil * (R - 1) - ph, dil * (S - 1) - pw, dil, S,
-                        g * Kg, Kg, k2]
-                _ext.gemm_conv_fwd(dyl, wrF[g * cgp:], dx2[:, g * Cg:],
-                                   None, _zpage(dy.device), N * H * W,
-                                   Cg, _pad32(k2), _pad32(k2), C, False,
-                                   dx_acc, geom)
-            return dx, dw, db
         if s2d:
             # the data gradient of a conv1-class layer is only asked for
             # in tests (no net propagates into the data layer): build
@@ -831,21 +881,181 @@ def conv2d_backward(x, w, dy, stride, pad, dilation, groups,
                              device=dy.device)[:Kout]
             wr[:, :Kcol] = _as_bf16(ctx["w_ref"]).permute(0, 2, 3, 1) \
                 .reshape(Kout, Kcol)
-        dcol = torch.empty((NPQ, Kpad), dtype=torch.bfloat16,
-                           device=dy.device)
+        # transposed packed weights for the dcol GEMM — maintained by the
+        # fused repack kernel for G==1, transposed in _conv_dx otherwise
+        wrT = getattr(ctx.get("w_ref"), "_cos_wrT", None) \
+            if G == 1 and not s2d else None
+        # the space-to-depth route is taken only where the implicit one
+        # is not, so it has no flipped layout: the wr built above is the
+        # operand _conv_dx uses
+        wrF = None if s2d else getattr(ctx.get("w_ref"), "_cos_wrF", None)
+        _conv_dx(dyl, _dyg, ld_dy, ctx["shape"], wr, wrT, wrF, dx, dx_acc)
+    return dx, dw, db
+
+
+# ---------------------------------------------------------- deconvolution
+# A transposed convolution with the caffe weight Wd[Ci][Co/G][R][S] is the
+# data gradient of the convolution whose weight [Kout=Ci][Cg=Co/G][R][S] is
+# Wd as it stands.  Strided G == 1 layers take the depth-to-space route
+# (csrc/d2s.hip): all st*st output phases are ONE stride-1 R'xS' implicit
+# GEMM over x with st*st*Co output channels, followed by a permutation.
+# Every other shape runs the convolution's own dx sequence (_conv_dx).
+
+# COS_DECONV_D2S when unset: the measured-faster route at both benchmark
+# shapes (BASELINE.md "Deconvolution")
+_DECONV_D2S_DEFAULT = "1"
+
+
+def _d2s_geom(N, Ci, Co, H, W, R, S, sh, sw, dil, G):
+    """(st, R', S', H', W', Kcol', Kpad') when the layer takes the
+    depth-to-space route, else None."""
+    if not (G == 1 and dil == 1 and sh == sw and sh >= 2 and Ci % 8 == 0):
+        return None
+    st = sh
+    Rp, Sp = -(-R // st), -(-S // st)
+    Hp, Wp = H + Rp - 1, W + Sp - 1
+    Kcol_d = Rp * Sp * Ci
+    # magic-divide bounds of gemm_conv_fwd
+    if N * Hp * Wp >= (1 << 20) or Kcol_d >= (1 << 20):
+        return None
+    if os.environ.get("COS_DECONV_D2S", _DECONV_D2S_DEFAULT) == "0":
+        return None
+    return (st, Rp, Sp, Hp, Wp, Kcol_d, _kpad_dma(Kcol_d))
+
+
+def _deconv2d_forward_d2s(x, w, b, d2s, Co, R, S, ph, pw, Ho, Wo, relu):
+    st, Rp, Sp, Hp, Wp, Kcol_d, Kpad_d = d2s
+    N, Ci, H, W = x.shape
+    Nz = st * st * Co
+    # the buffer is kept under an attribute of its own: _cos_wrb/wrT/wrF
+    # belong to the convolution the backward pass runs on the same tensor.
+    # Pad rows and columns are zeroed here once; the pack rewrites the
+    # whole live region on every call (weights change every step).
+    wrD = getattr(w, "_cos_wrD", None)
+    if wrD is None or wrD.shape != (_pad128(Nz), Kpad_d) \
+            or wrD.device != x.device:
+        wrD = torch.zeros((_pad128(Nz), Kpad_d), dtype=torch.bfloat16,
+                          device=x.device)
+        w._cos_wrD = wrD
+    _ext.d2s_pack_weight(_as_bf16(w).contiguous(), wrD, Ci, Co, R, S, st,
+                         Kpad_d)
+    bias_z = b.float().repeat(st * st).contiguous() if b is not None \
+        else None
+    xl = _cl(x)
+    M = N * Hp * Wp
+    z = torch.empty((M, Nz), dtype=torch.bfloat16, device=x.device)
+    geom = [H, W, Ci, Hp, Wp, 1, 1, Rp - 1, Sp - 1, 1, Sp, 0, Ci, Kcol_d]
+    _ext.gemm_conv_fwd(xl, wrD, z, bias_z, _zpage(x.device), M, Nz, Kpad_d,
+                       Kpad_d, Nz, relu, False, geom)
+    y = torch.empty((N, Co, Ho, Wo), dtype=torch.bfloat16, device=x.device,
+                    memory_format=torch.channels_last)
+    _ext.d2s_unpack(z, y, st, ph, pw, Hp, Wp)
+    return y
+
+
+def _deconv2d_forward_col2im(x, w, b, shape, relu):
+    """Every shape the depth-to-space route does not take: the dx sequence
+    of the convolution (x plays the top gradient), then bias and ReLU."""
+    (N, C, H, W, P, Q, R, S, sh, sw, ph, pw, dil, G, Cg, Kg, Kpad,
+     Kcol) = shape
+    Kout = Kg * G
+    xl = _cl(x)
+    x2 = xl.permute(0, 2, 3, 1).reshape(N * P * Q, Kout)
+    wb = _as_bf16(w)
+    wr = wrF = None
+    if _conv_implicit_ok(N, C, Cg, R, S, P, Q) and \
+            _dx_imp_ok(N, H, W, R, S, sh, sw, ph, pw, dil, Kg):
+        # flipped per-group layout wrF[g][c][(RS-1-rs)*Kg + k], as
+        # conv2d_forward builds it
+        k2, cgp = R * S * Kg, _pad128(Cg)
+        wrF = getattr(w, "_cos_dcv_wrF", None)
+        if wrF is None or wrF.shape != (G * cgp, _kpad_dma(k2)) \
+                or wrF.device != x.device:
+            wrF = torch.zeros((G * cgp, _kpad_dma(k2)),
+                              dtype=torch.bfloat16,
+                              device=x.device)
+            w._cos_dcv_wrF = wrF
+        wf = wb.flip(2, 3)
         for g in range(G):
-            # dcol[npq, kpad] = dy_g[npq, kg] @ w_g[kg, kpad]: transposed
-            # packed weights — maintained by the fused repack kernel for
-            # G==1, transposed here otherwise
-            wrT = getattr(ctx.get("w_ref"), "_cos_wrT", None) \
-                if G == 1 and not s2d else None
-            if wrT is None:
-                wrT = _transpose(wr[g * Kg:(g + 1) * Kg].contiguous())
-            _gemm(_dyg(g), wrT, dcol, None,
-                  NPQ, Kpad, Kg, ld_dy, Kg, Kpad, False, False, 0, 1,
-                  ma=NPQ, na=_pad128(Kpad))
-            _ext.col2im(dcol, dx, N, H, W, C, P, Q, R, S, sh, sw, ph, pw,
-                        dil, Kpad, g * Cg, Cg)
+            wrF[g * cgp:g * cgp + Cg, :k2] = \
+                wf[g * Kg:(g + 1) * Kg].permute(1, 2, 3, 0).reshape(Cg, k2)
+    else:
+        wr = getattr(w, "_cos_dcv_wr", None)
+        if wr is None or wr.shape != (_pad128(Kout), Kpad) \
+                or wr.device != x.device:
+            wr = torch.zeros((_pad128(Kout), Kpad), dtype=torch.bfloat16,
+                             device=x.device)
+            w._cos_dcv_wr = wr
+        wr[:Kout, :Kcol] = wb.permute(0, 2, 3, 1).reshape(Kout, Kcol)
+    y = torch.empty((N, C, H, W), dtype=torch.bfloat16, device=x.device,
+                    memory_format=torch.channels_last)
+    _conv_dx(xl, lambda g: x2[:, g * Kg:] if g else x2, Kout, shape, wr,
+             None, wrF, y)
+    if b is not None:
+        y = reference.bias_add(y, b.to(y.dtype))
+    return relu_forward(y) if relu else y
+
+
+def deconv2d_forward(x, w, b, stride, pad, dilation, groups, ctx=None,
+                     relu=False):
+    _check_bf16(x, "deconv input")
+    sh, sw = stride
+    ph, pw = pad
+    dil = dilation[0]
+    N, Ci, H, W = x.shape
+    G = groups
+    Cog, R, S = w.shape[1], w.shape[2], w.shape[3]
+    if w.shape[0] != Ci or Ci % G != 0:
+        raise ValueError(f"deconv weight {tuple(w.shape)} does not match "
+                         f"{Ci} input channels in {G} groups")
+    Co = Cog * G
+    Ho = sh * (H - 1) + dil * (R - 1) + 1 - 2 * ph
+    Wo = sw * (W - 1) + dil * (S - 1) + 1 - 2 * pw
+    if Ho <= 0 or Wo <= 0:
+        raise ValueError("deconv output is empty")
+    d2s = _d2s_geom(N, Ci, Co, H, W, R, S, sh, sw, dil, G)
+    if d2s is not None:
+        y = _deconv2d_forward_d2s(x, w, b, d2s, Co, R, S, ph, pw, Ho, Wo,
+                                  relu)
+    else:
+        Kcol = R * S * Cog
+        # the convolution whose data gradient this is: input
+        # [N, Co, Ho, Wo] -> output [N, Ci, H, W]
+        shape = (N, Co, Ho, Wo, H, W, R, S, sh, sw, ph, pw, dil, G, Cog,
+                 Ci // G, _pad8(Kcol), Kcol)
+        y = _deconv2d_forward_col2im(x, w, b, shape, relu)
+    if ctx is not None:
+        ctx["route"] = "d2s" if d2s is not None else "col2im"
+    return y
+
+
+def deconv2d_backward(x, w, dy, stride, pad, dilation, groups,
+                      need_dx=True, need_dw=True, bias=True, ctx=None,
+                      dw_out=None, db_out=None):
+    # ctx (the forward pass's) is not read: nothing the depth-to-space
+    # forward builds serves the backward convolution, whose own context
+    # conv2d_forward fills below
+    _check_bf16(dy, "deconv dy")
+    dx = dw = db = None
+    c = {}
+    if need_dx:
+        # the forward pass of the convolution; it also fills the context
+        # the weight gradient reads
+        dx = conv2d_forward(dy, w, None, stride, pad, dilation, groups,
+                            ctx=c)
+    if need_dw:
+        # the convolution's weight gradient with the roles of the two
+        # activations exchanged; it lands in Wd's own layout
+        _, dw, _ = conv2d_backward(dy, w, x, stride, pad, dilation, groups,
+                                   need_dx=False, need_dw=True, bias=False,
+                                   ctx=c, dw_out=dw_out)
+    if bias:
+        N, Co, Ho, Wo = dy.shape
+        dyl = _cl(dy)
+        db = db_out if db_out is not None \
+            else _scratch_buf((Co,), torch.float32, dy.device)
+        _ext.colsum(dyl.permute(0, 2, 3, 1).reshape(N * Ho * Wo, Co), db,
+                    N * Ho * Wo, Co, Co)
     return dx, dw, db
 
 

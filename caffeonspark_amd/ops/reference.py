@@ -46,6 +46,44 @@ def conv2d_backward(x, w, dy, stride, pad, dilation, groups,
     return dx, dw, db
 
 
+# ------------------------------------------------------------- deconvolution
+
+def deconv2d_forward(x, w, b, stride, pad, dilation, groups, ctx=None,
+                     relu=False):
+    """Transposed convolution, caffe layout: x [N, Ci, H, W],
+    w [Ci, Co/groups, R, S], b [Co] or None."""
+    if b is not None and b.dtype != x.dtype:
+        b = b.to(x.dtype)   # callers pass the fp32 master bias
+    y = F.conv_transpose2d(x, w, b, stride=stride, padding=pad,
+                           dilation=dilation, groups=groups)
+    return F.relu(y) if relu else y
+
+
+def deconv2d_backward(x, w, dy, stride, pad, dilation, groups,
+                      need_dx=True, need_dw=True, bias=True, ctx=None,
+                      dw_out=None, db_out=None):
+    """A transposed convolution is the data gradient of the convolution
+    whose weight [Kout=Ci][C=Co/groups][R][S] is w as it stands, so its own
+    data gradient is that convolution's forward pass over dy, and its
+    weight gradient that convolution's weight gradient with x and dy
+    exchanged."""
+    # ctx, db_out: GPU-path hints, unused here
+    dx = dw = db = None
+    if need_dx:
+        dx = F.conv2d(dy, w, None, stride=stride, padding=pad,
+                      dilation=dilation, groups=groups)
+    if need_dw:
+        dw = torch.nn.grad.conv2d_weight(dy, list(w.shape), x, stride=stride,
+                                         padding=pad, dilation=dilation,
+                                         groups=groups)
+        if dw_out is not None:
+            dw_out.copy_(dw)
+            dw = dw_out
+    if bias:
+        db = dy.sum(dim=(0, 2, 3))
+    return dx, dw, db
+
+
 # ------------------------------------------------------------- inner product
 
 def fc_forward(x, w, b, relu=False):

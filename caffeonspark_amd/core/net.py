@@ -379,6 +379,26 @@ class Net:
         return [l for l in self.layers
                 if isinstance(l, (MemoryDataLayer, CoSDataLayer))]
 
+    # -------------------------------------------------------- recurrent state
+    # read by recurrent layers at setup; off unless a caller opts in
+    recurrent_stateful = False
+
+    def _recurrent_layers(self):
+        return [l for l in self.layers if hasattr(l, "reset_state")]
+
+    def set_recurrent_stateful(self, on: bool = True) -> None:
+        """Make every recurrent layer carry (h, c) from one forward to
+        the next (token-by-token decode: T = 1 per forward, cont = 0
+        restarts a stream).  Clears any saved state."""
+        self.recurrent_stateful = bool(on)
+        for l in self._recurrent_layers():
+            l.stateful = bool(on)
+            l.reset_state()
+
+    def reset_recurrent_state(self) -> None:
+        for l in self._recurrent_layers():
+            l.reset_state()
+
     # ---------------------------------------------------------------- sharing
     def share_trained_layers_with(self, other: "Net") -> None:
         """Point this net's param blobs at `other`'s (reference:

@@ -170,6 +170,12 @@ void lstm_seq_bwd(const void* dy, const void* w_hcT, const void* cont,
                   void* dxg, void* dh_rec, float* dh_f, float* dc_a,
                   float* dc_b, int T, int N, int H, int n_alloc_whcT,
                   hipStream_t stream);
+int64_t lstm_step_lds_bytes(int N, int D, int H, int Ds);
+void lstm_step(const void* x, const void* h_prev, const void* xs,
+               const void* w_xc, const void* w_hc, const void* w_xsc,
+               const void* bias, const float* cont, const float* c_prev,
+               float* c_out, void* h_out, int N, int D, int H, int Ds,
+               hipStream_t stream);
 void softmax_loss_fwd(const void* x, const float* label, float* prob,
                       float* rowloss, float* loss, int* count,
                       int64_t nrows, int C, int ignore, bool has_ignore,
@@ -768,6 +774,63 @@ void py_lstm_unit_bwd(Tensor c_prev, Tensor c_out, Tensor act, Tensor cont,
                         cur_stream());
 }
 
+int64_t py_lstm_step_lds_bytes(int64_t N, int64_t D, int64_t H, int64_t Ds) {
+  const int64_t lim = 1 << 24;
+  if (N < 0 || D < 0 || H < 0 || Ds < 0 || N >= lim || D >= lim ||
+      H >= lim || Ds >= lim)
+    return -1;
+  return cosamd::lstm_step_lds_bytes((int)N, (int)D, (int)H, (int)Ds);
+}
+
+// one decode token of one LSTM layer; every operand is checked against the
+// extent the kernel reads or writes (16-byte loads: aligned, contiguous)
+void py_lstm_step(Tensor x, Tensor h_prev, c10::optional<Tensor> xs,
+                  Tensor w_xc, Tensor w_hc, c10::optional<Tensor> w_xsc,
+                  Tensor bias, Tensor cont, Tensor c_prev, Tensor c_out,
+                  Tensor h_out) {
+  TORCH_CHECK(x.dim() == 2 && h_prev.dim() == 2, "lstm_step: 2-D x, h_prev");
+  int64_t N = x.size(0), D = x.size(1), H = h_prev.size(1);
+  int64_t Ds = xs.has_value() ? xs.value().size(-1) : 0;
+  TORCH_CHECK(xs.has_value() == w_xsc.has_value(),
+              "lstm_step: x_static and W_xsc go together");
+  TORCH_CHECK(py_lstm_step_lds_bytes(N, D, H, Ds) >= 0,
+              "lstm_step: shape outside the fused kernel");
+  auto bf = [&](const Tensor& t, int64_t r, int64_t c, const char* what) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 &&
+                t.is_contiguous() && t.numel() == r * c &&
+                reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+                "lstm_step: ", what, " must be contiguous 16-byte aligned "
+                "bf16 of ", r, "x", c);
+  };
+  auto f32 = [&](const Tensor& t, int64_t n, const char* what) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat &&
+                t.is_contiguous() && t.numel() == n,
+                "lstm_step: ", what, " must be contiguous fp32 of ", n);
+  };
+  bf(x, N, D, "x"); bf(h_prev, N, H, "h_prev");
+  bf(w_xc, 4 * H, D, "W_xc"); bf(w_hc, 4 * H, H, "W_hc");
+  bf(h_out, N, H, "h_out");
+  TORCH_CHECK(bias.is_cuda() && bias.scalar_type() == at::kBFloat16 &&
+              bias.is_contiguous() && bias.numel() == 4 * H,
+              "lstm_step: bias must be contiguous bf16 of 4H");
+  const void* xsp = nullptr;
+  const void* wsp = nullptr;
+  if (Ds) {
+    bf(xs.value(), N, Ds, "x_static"); bf(w_xsc.value(), 4 * H, Ds, "W_xsc");
+    xsp = xs.value().data_ptr();
+    wsp = w_xsc.value().data_ptr();
+  }
+  f32(cont, N, "cont"); f32(c_prev, N * H, "c_prev"); f32(c_out, N * H, "c");
+  TORCH_CHECK(h_out.data_ptr() != h_prev.data_ptr() &&
+              c_out.data_ptr() != c_prev.data_ptr(),
+              "lstm_step: outputs must not alias the previous state");
+  cosamd::lstm_step(x.data_ptr(), h_prev.data_ptr(), xsp, w_xc.data_ptr(),
+                    w_hc.data_ptr(), wsp, bias.data_ptr(),
+                    cont.data_ptr<float>(), c_prev.data_ptr<float>(),
+                    c_out.data_ptr<float>(), h_out.data_ptr(), (int)N,
+                    (int)D, (int)H, (int)Ds, cur_stream());
+}
+
 void py_embed_fwd(Tensor idx, Tensor w, Tensor y, int64_t V) {
   CHECK_F32(idx); CHECK_BF16(w);
   cosamd::embed_fwd(idx.data_ptr<float>(), w.data_ptr(), y.data_ptr(),
@@ -924,6 +987,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lstm_seq_bwd", &py_lstm_seq_bwd);
   m.def("lstm_unit_fwd", &py_lstm_unit_fwd);
   m.def("lstm_unit_bwd", &py_lstm_unit_bwd);
+  m.def("lstm_step", &py_lstm_step);
+  m.def("lstm_step_lds_bytes", &py_lstm_step_lds_bytes);
   m.def("embed_fwd", &py_embed_fwd);
   m.def("embed_bwd", &py_embed_bwd);
   m.def("softmax_loss_fwd", &py_softmax_loss_fwd);

@@ -1691,6 +1691,43 @@ def lstm_unit_backward(c_prev, cache, dc_next, dh):
     return dc_prev, dgates
 
 
+# ---- fused decode step (csrc/lstm_step.hip): one launch per LSTM layer
+# per token at T == 1.  COS_LSTM_STEP=0 turns the route off;
+# COS_LSTM_STEP_MAXN bounds the streams it serves (BASELINE.md "Caption
+# decode"; the kernel itself stops at 16).
+_LSTM_STEP_MAXN_DEFAULT = "16"
+
+
+def lstm_step_ok(N, D, H, Ds, tensors=()):
+    """True when a T == 1 step of these dims takes the fused kernel: bf16
+    operands it can read in place (contiguous, 16-byte aligned rows),
+    N within COS_LSTM_STEP_MAXN and the activation panel within the
+    kernel's LDS budget."""
+    if os.environ.get("COS_LSTM_STEP", "1") == "0":
+        return False
+    if N > int(os.environ.get("COS_LSTM_STEP_MAXN", _LSTM_STEP_MAXN_DEFAULT)):
+        return False
+    if _ext.lstm_step_lds_bytes(N, D, H, Ds) < 0:
+        return False
+    return all(t.dtype == torch.bfloat16 and t.is_contiguous()
+               and t.data_ptr() % 16 == 0 for t in tensors)
+
+
+def lstm_step(x, h_prev, c_prev, cont, w_xc, b_c, w_hc, xs=None,
+              w_xsc=None):
+    """One token of one LSTM layer.  x [N,D], h_prev [N,H] bf16, c_prev
+    [N,H] fp32, cont [N]; the weights are read where they lie (no copy,
+    no pad).  Returns fresh (h bf16, c fp32): the previous state is only
+    read, other blocks of the launch still need it."""
+    N, H = h_prev.shape
+    cont_f = cont.reshape(N).float().contiguous()
+    h = torch.empty((N, H), dtype=torch.bfloat16, device=x.device)
+    c = torch.empty((N, H), dtype=torch.float32, device=x.device)
+    _ext.lstm_step(x, h_prev, xs, w_xc, w_hc, w_xsc, b_c, cont_f,
+                   c_prev.contiguous(), c, h)
+    return h, c
+
+
 def lstm_seq_forward(xg, w_hc, cont):
     """Whole-sequence LSTM forward driven from C++ (3 launches/step).
     xg: [T,N,4H] pre-activation input gates (x @ W_xc + b [+ static]),

@@ -50,11 +50,19 @@ class _BlobView:
     def shape(self):
         return tuple(self._blob.shape)
 
+    def reshape(self, *dims) -> None:
+        """pycaffe's blob.reshape(*dims): a zero blob of the new shape
+        (a no-op when the shape already matches)."""
+        if len(dims) == 1 and isinstance(dims[0], (tuple, list)):
+            dims = tuple(dims[0])
+        self._blob.reshape([int(d) for d in dims])
+
 
 class Net:
     def __init__(self, proto_file: str, weights: Optional[str] = None,
                  phase: int = TEST, *, stages: Optional[List[str]] = None,
-                 device: Optional[torch.device] = None):
+                 device: Optional[torch.device] = None,
+                 stateful_recurrent: bool = True):
         state = caffe_pb.NetState(phase=phase, stage=list(stages or []))
         dtype = torch.bfloat16 if (device is not None and
                                    device.type == "cuda") else torch.float32
@@ -67,6 +75,9 @@ class Net:
             else:
                 self._net.copy_trained_layers_from(
                     read_binary_proto(weights, caffe_pb.NetParameter))
+        # upstream pycaffe's recurrent layers keep h/c between forward()
+        # calls (the captioning scripts step one token per call)
+        self._net.set_recurrent_stateful(stateful_recurrent)
         self.blobs: Dict[str, _BlobView] = {
             name: _BlobView(b) for name, b in self._net.blob_map.items()}
         self.params: Dict[str, List[_BlobView]] = {
@@ -79,6 +90,15 @@ class Net:
         self._net.forward()
         return {name: self.blobs[name].data
                 for name in self._net.output_blob_names()}
+
+    def reshape(self) -> None:
+        """pycaffe's net.reshape(): nothing to do, layers take their
+        shapes from the bottoms on every forward."""
+        return None
+
+    def reset_recurrent_state(self) -> None:
+        """Zero the h/c that stateful recurrent layers carry."""
+        self._net.reset_recurrent_state()
 
     def backward(self) -> Dict[str, np.ndarray]:
         """pycaffe-style backward: populate blob diffs from the loss tops

@@ -1198,6 +1198,11 @@ void gemm_bf16_batched(const void* A_, const void* B_, void* C,
                    BGuarded{B, ldb}, stream);
     return;
   }
+  // every split-K block runs the fp32 epilogue: a bias would be added and
+  // the ReLU applied once per split, on partial sums
+  if (sk.zblocks > 1 && (bias != nullptr || relu))
+    throw std::runtime_error(
+        "gemm: split-K cannot fuse bias or ReLU; finish with bias_act_cast");
   if (!trans_a && !trans_b) {
     if (use_w8(M, N)) {
       if (store_mode == 0)      COS_GEMM_CASE8(0);

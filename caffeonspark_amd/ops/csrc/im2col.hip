@@ -252,7 +252,12 @@ __global__ void col2im_nhwc_kernel(
 void im2col_nhwc(const void* x, void* col, int N, int H, int W, int C,
                  int P, int Q, int R, int S, int sh, int sw, int ph, int pw,
                  int dil, int Kpad, int c0, int Ct, hipStream_t stream) {
-  if (Kpad <= 2560) {
+  // the LUT kernel packs (dh<<20)|(dw<<10)|c into one non-negative int:
+  // a channel offset >= 1024 would carry into dw (1x1 stride-2 / padded
+  // convs with Cg > 1024), so it runs only when every field fits
+  bool lut_fits = Ct <= 1024 && (int64_t)dil * (S - 1) < 1024 &&
+                  (int64_t)dil * (R - 1) < 2048;
+  if (Kpad <= 2560 && lut_fits) {
     int64_t total8 = (int64_t)N * P * Q * (Kpad / 8);
     int b = hmin<int64_t>(8192, (total8 + 255) / 256);
     im2col_smallc_kernel<<<b, 256, 0, stream>>>(

@@ -270,26 +270,40 @@ class ReLULayer(Layer):
         if not propagate_down[0]:
             return
         if self.__dict__.pop("_mask_done_step", False):
-            # the fused concat already applied this ReLU's mask densely
+            # the fused concat (or the fused max-pool backward above this
+            # ReLU) already applied this ReLU's mask
+            self._route = "mask_done"
             self.acc_blob_diff(bottom[0], top[0].diff,
                                top[0] is bottom[0])
             return
+        self._route = "plain"
         prod = getattr(self, "_db_producer", None)
         db_out = None
         import os as _os
         if prod is not None and self.net._ops_mode == "bf16" \
-                and bool(int(_os.environ.get("COS_RELU_DB", "0"))):
-            # fused relu'+colsum measured SLOWER than the two separate
-            # passes (AlexNet 54.1k->52.6k, GoogLeNet 10.77k->10.30k,
-            # same-box A/B): the column-strip block shape the reduction
-            # needs costs more dx-write coalescing than the saved dy
-            # read.  Kept behind COS_RELU_DB=1 for evidence.
+                and bool(int(_os.environ.get("COS_RELU_DB", "1"))):
+            # (round 2) fused relu'+colsum measured SLOWER than the two
+            # separate passes (AlexNet 54.1k->52.6k, GoogLeNet
+            # 10.77k->10.30k, same-box A/B): the column-strip block shape
+            # the reduction needs costs more dx-write coalescing than the
+            # saved dy read.  Kept behind COS_RELU_DB=1 for evidence.
+            #
+            # Correction: the block shape was not the cause; a block trip
+            # of that kernel covers whole rows.  Its up to 4096 blocks
+            # each end in one float atomic per column onto the same
+            # addresses, ~25 ns per adder measured (docs/
+            # ROUND2_EXPERIMENTS.md item 17, dated correction).
+            # Dense C % 8 == 0 tensors now take relu_db_dense (register
+            # partials, 4 row loads in flight, a bounded grid), and the
+            # fusion is on by default; COS_RELU_DB=0 restores the
+            # separate relu_bwd + colsum kernels.
             db_out = prod._bias_arena()
         if db_out is not None:
             dx, done = ops.relu_backward(top[0].data, top[0].diff,
                                          self.slope, db_out=db_out)
             if done:
                 prod._db_done_step = True
+                self._route = "relu_db"
         else:
             dx = ops.relu_backward(top[0].data, top[0].diff, self.slope)
         self.acc_blob_diff(bottom[0], dx, top[0] is bottom[0])
@@ -366,8 +380,38 @@ class PoolingLayer(Layer):
                                       (self.sh, self.sw),
                                       (self.ph, self.pw), dy)
         else:
-            dx = ops.maxpool_backward(list(x.shape), self._idx, dy)
+            dx = self._backward_relu_db(dy)
+            if dx is None:
+                dx = ops.maxpool_backward(list(x.shape), self._idx, dy)
         self.acc_blob_diff(bottom[0], dx, False)
+
+    def _backward_relu_db(self, dy):
+        """conv -> in-place ReLU -> this pool (Net._fuse_relu_pool_peephole):
+        one kernel routes dy, applies the ReLU mask and sums the conv's
+        bias gradient.  Returns the masked dx and flags the ReLU and the
+        conv to skip their share, or None (no flag set) when the fused
+        kernel does not apply this step."""
+        self._route = "plain"
+        fuse = getattr(self, "_relu_db_fuse", None)
+        import os as _os
+        if fuse is None or self.net._ops_mode != "bf16" \
+                or not bool(int(_os.environ.get("COS_RELU_DB", "1"))):
+            return None
+        relu, conv = fuse
+        if conv.blobs[1]._lr_mult == 0 or dy is None \
+                or dy.dtype != torch.bfloat16 or len(self._idx) < 4:
+            return None
+        db_out = conv._bias_arena()
+        fn = ops.gpu_op("maxpool_backward_relu_db")
+        if db_out is None or fn is None:
+            return None
+        dx = fn(self._idx, dy, db_out)
+        if dx is None:
+            return None
+        relu._mask_done_step = True
+        conv._db_done_step = True
+        self._route = "relu_db"
+        return dx
 
 
 @register_layer("LRN")

@@ -161,6 +161,7 @@ class Net:
                 if w != 0.0:
                     self._loss_tops.append((idx, ti, w))
         self._fuse_relu_peephole()
+        self._fuse_relu_pool_peephole()
         self._fuse_concat_peephole()
 
     def _fuse_relu_peephole(self) -> None:
@@ -185,6 +186,41 @@ class Net:
                 # backward fusion: the ReLU's gradient pass also column-
                 # sums the producer's bias gradient into the arena
                 b._db_producer = a
+
+    def _fuse_relu_pool_peephole(self) -> None:
+        """Convolution -> fused in-place ReLU (slope 0) -> MAX Pooling, the
+        pool being the ReLU blob's only consumer: the pool's backward also
+        applies the ReLU mask and sums the conv's bias gradient
+        (PoolingLayer._backward_relu_db).  Dtype, the pre-zeroed bias
+        arena and the kernel's shape limits are checked at backward
+        time."""
+        if self.device.type != "cuda" or self._ops_mode != "bf16":
+            return
+        # readers of each blob, and the layers that rewrite it in place
+        consumers: dict = {}
+        inplace: dict = {}
+        for l in self.layers:
+            tops = set(l.param.top)
+            for bn in l.param.bottom:
+                (inplace if bn in tops else consumers).setdefault(
+                    bn, []).append(l)
+        out_names = set(self.output_blob_names())
+        for conv, relu in zip(self.layers, self.layers[1:]):
+            if getattr(relu, "_db_producer", None) is not conv \
+                    or conv.param.type != "Convolution":
+                continue
+            bn = relu.param.top[0]
+            users = consumers.get(bn, [])
+            if len(users) != 1 or bn in out_names \
+                    or inplace.get(bn, []) != [relu]:
+                continue
+            pool = users[0]
+            if pool.param.type != "Pooling" or pool.global_pooling or \
+                    pool.method != caffe_pb.PoolingParameter.PoolMethod.MAX:
+                continue
+            if conv.num_output % 8 != 0 or pool.kh * pool.kw >= 128:
+                continue        # scalar pooling kernels / int32 argmax
+            pool._relu_db_fuse = (relu, conv)
 
     def _fuse_concat_peephole(self) -> None:
         """Inception fusion (GPU): when every input of a channel Concat

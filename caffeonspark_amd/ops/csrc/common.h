@@ -46,6 +46,13 @@ __device__ __forceinline__ int xcd_swizzle(int bid, int nwg) {
 }
 
 
+// Grid cap of the persistent kernels that end in one float atomic per
+// (block, column) onto a bias gradient (relu_db_dense, maxpool_bwd8_relu_db):
+// 2 blocks per CU on the 256-CU MI355X.  Every block adds into the same C
+// addresses, where float atomics serialise, so the block count is also the
+// number of adders per address.
+constexpr int kFusedDbBlocks = 512;
+
 // host-side min/max (avoid relying on device overloads in host code)
 template <typename T> static inline T hmin(T a, T b) { return a < b ? a : b; }
 template <typename T> static inline T hmax(T a, T b) { return a > b ? a : b; }

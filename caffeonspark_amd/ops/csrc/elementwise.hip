@@ -534,6 +534,78 @@ __global__ void relu_colsum_bwd_kernel(
   }
 }
 
+// Dense fast route of the fused ReLU' + db pass: y, dy and dx are dense
+// [rows][C], C % 8 == 0.  blockDim.x == bx*by exactly; grid.x = column
+// strips of bx octets (one strip when a whole row fits a block, so a block
+// trip reads and writes by contiguous rows), grid.y = row blocks.  A
+// thread keeps one octet for its whole life, so its 8 fp32 partials stay
+// in registers; the row loop is unrolled 4x with all 8 loads issued
+// before the first use.  One LDS reduce and one atomic per (block,
+// column): the launcher bounds grid.y, and with it the adders per db
+// address (the float atomics serialise when every block adds into the
+// same row of addresses).
+__device__ __forceinline__ void relu_db_octet(const u16x8& vy,
+                                              const u16x8& vd, float slope,
+                                              float* acc, u16* dx) {
+  u16x8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float fy = ldbf((const u16*)&vy + j);
+    float fd = ldbf((const u16*)&vd + j);
+    float g = fy > 0.f ? fd : fd * slope;
+    acc[j] += g;
+    bf16 b = f2bf(g);
+    o[j] = *reinterpret_cast<u16*>(&b);
+  }
+  *reinterpret_cast<u16x8*>(dx) = o;
+}
+
+__global__ void __launch_bounds__(1024) relu_db_dense_kernel(
+    const u16* __restrict__ y, const u16* __restrict__ dy,
+    u16* __restrict__ dx, float* __restrict__ db, float slope,
+    int64_t rows, int C, int bx) {
+  __shared__ float part[8192];           // by * bx * 8 <= 1024*8
+  int by = blockDim.x / bx;
+  int c8 = threadIdx.x % bx;
+  int rg = threadIdx.x / bx;
+  int c = (blockIdx.x * bx + c8) * 8;
+  float acc[8] = {};
+  if (c < C) {
+    int64_t stride = (int64_t)gridDim.y * by;
+    int64_t step = stride * C;
+    int64_t r = (int64_t)blockIdx.y * by + rg;
+    int64_t off = r * C + c;
+    for (; r + 3 * stride < rows; r += 4 * stride, off += 4 * step) {
+      u16x8 vy[4], vd[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        vy[k] = *reinterpret_cast<const u16x8*>(y + off + k * step);
+        vd[k] = *reinterpret_cast<const u16x8*>(dy + off + k * step);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        relu_db_octet(vy[k], vd[k], slope, acc, dx + off + k * step);
+    }
+    for (; r < rows; r += stride, off += step) {
+      u16x8 vy = *reinterpret_cast<const u16x8*>(y + off);
+      u16x8 vd = *reinterpret_cast<const u16x8*>(dy + off);
+      relu_db_octet(vy, vd, slope, acc, dx + off);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) part[rg * bx * 8 + c8 * 8 + j] = acc[j];
+  __syncthreads();
+  int pass_cols = bx * 8;
+  for (int col = threadIdx.x; col < pass_cols; col += blockDim.x) {
+    int oc = blockIdx.x * pass_cols + col;
+    if (oc < C) {
+      float sum = 0.f;
+      for (int g = 0; g < by; ++g) sum += part[g * pass_cols + col];
+      atomicAdd(db + oc, sum);
+    }
+  }
+}
+
 // 8-wide column reduce with adaptive block shape: bx col-groups (8
 // bf16 columns = one 16-byte load each) x by row-groups, bx sized to
 // the matrix so narrow matrices (conv bias grads, cols 96-384) still
@@ -810,6 +882,35 @@ void relu_colsum_bwd(const void* y, const void* dy, void* dx, float* db,
   relu_colsum_bwd_kernel<<<blocks, nthreads, 0, stream>>>(
       (const u16*)y, (const u16*)dy, (u16*)dx, db, slope, rows, cols,
       ldy, lddy, bx);
+}
+
+// Dense route (C % 8 == 0, ldy == lddy == C).  row_blocks > 0 forces
+// grid.y (tests: 1, 2, 3 blocks on tiny data); 0 sizes it: at most
+// kFusedDbBlocks blocks chip-wide (2 per CU), fewer for small matrices
+// (>= 16 elements per thread), never more row blocks than rows need.
+constexpr int64_t kReluDbBigElems = int64_t(1) << 22;
+
+void relu_db_dense(const void* y, const void* dy, void* dx, float* db,
+                   float slope, int64_t rows, int C, int row_blocks,
+                   hipStream_t stream) {
+  int nc8 = C / 8;
+  int bx = nc8 <= 128 ? nc8 : 32;        // whole rows, or 512-byte strips
+  // big activations: 1024-thread blocks keep the CUs full of loads at
+  // half the blocks, so half the adders per db address
+  int threads = rows * (int64_t)C >= kReluDbBigElems ? 1024 : 256;
+  int by = threads / bx;
+  int strips = (nc8 + bx - 1) / bx;
+  int64_t need = (rows + by - 1) / by;
+  int64_t gy = row_blocks;
+  if (gy <= 0) {
+    int64_t work_blocks = (rows * (int64_t)C) / (256 * 16) + 1;
+    int64_t cap = hmin<int64_t>(
+        threads == 1024 ? kFusedDbBlocks / 2 : kFusedDbBlocks, work_blocks);
+    gy = hmin<int64_t>(need, hmax<int64_t>(1, cap / strips));
+  }
+  gy = hmax<int64_t>(1, hmin<int64_t>(gy, 65535));
+  relu_db_dense_kernel<<<dim3(strips, (unsigned)gy), bx * by, 0, stream>>>(
+      (const u16*)y, (const u16*)dy, (u16*)dx, db, slope, rows, C, bx);
 }
 
 void colsum(const void* in, float* out, int64_t rows, int cols, int ld,

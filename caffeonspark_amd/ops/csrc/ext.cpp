@@ -103,6 +103,10 @@ void maxpool_fwd(const void* x, void* y, void* idx, bool idx16, int N,
 void maxpool_bwd(const void* dy, const void* idx, bool idx16, void* dx,
                  int N, int H, int W, int C, int P, int Q, int kh, int kw,
                  int sh, int sw, int ph, int pw, hipStream_t stream);
+void maxpool_bwd8_relu_db(const void* dy, const void* idx, const void* top,
+                          void* dx, float* db, int N, int H, int W, int C,
+                          int P, int Q, int kh, int kw, int sh, int sw,
+                          int ph, int pw, int blocks, hipStream_t stream);
 void avgpool_fwd(const void* x, void* y, int N, int H, int W, int C,
                  int P, int Q, int kh, int kw, int sh, int sw, int ph, int pw,
                  hipStream_t stream);
@@ -145,6 +149,9 @@ void sgd_update_multi(float* p, const float* g, float* v,
                       const int64_t* seg_off, const float* seg_lr,
                       const float* seg_wd, int nseg, float mu,
                       int64_t total, void* sh, hipStream_t stream);
+void relu_db_dense(const void* y, const void* dy, void* dx, float* db,
+                   float slope, int64_t rows, int C, int row_blocks,
+                   hipStream_t stream);
 void colsum(const void* in, float* out, int64_t rows, int cols, int ld,
             hipStream_t stream);
 void transpose_bf16(const void* in, void* out, int64_t R, int64_t C,
@@ -362,6 +369,25 @@ void py_relu_colsum_bwd(Tensor y, Tensor dy, Tensor dx, Tensor db,
                           (int)cols, (int)ldy, (int)lddy, cur_stream());
 }
 
+// dense [rows][C] fast route; row_blocks 0 = auto (see relu_db_dense)
+void py_relu_db_dense(Tensor y, Tensor dy, Tensor dx, Tensor db,
+                      double slope, int64_t rows, int64_t C,
+                      int64_t row_blocks) {
+  CHECK_CUDA(y); CHECK_BF16(y); CHECK_BF16(dy); CHECK_BF16(dx);
+  CHECK_F32(db);
+  TORCH_CHECK(C > 0 && C % 8 == 0, "relu_db_dense needs C % 8 == 0");
+  TORCH_CHECK(rows >= 0 && y.numel() >= rows * C && dy.numel() >= rows * C &&
+              dx.numel() >= rows * C && db.numel() >= C,
+              "relu_db_dense: tensors smaller than rows x C");
+  TORCH_CHECK(y.is_contiguous() && dy.is_contiguous() &&
+              dx.is_contiguous() && db.is_contiguous(),
+              "relu_db_dense needs dense [rows][C] tensors");
+  TORCH_CHECK(row_blocks >= 0 && row_blocks <= 65535, "row_blocks");
+  cosamd::relu_db_dense(y.data_ptr(), dy.data_ptr(), dx.data_ptr(),
+                        db.data_ptr<float>(), (float)slope, rows, (int)C,
+                        (int)row_blocks, cur_stream());
+}
+
 void py_gemm_conv_fwd_sc(Tensor X, Tensor B, Tensor C,
                          c10::optional<Tensor> bias, int64_t M,
                          int64_t N, int64_t K, int64_t ldb, int64_t ldc,
@@ -436,6 +462,28 @@ void py_maxpool_bwd(Tensor dy, Tensor idx, Tensor dx, int64_t N, int64_t H,
   cosamd::maxpool_bwd(dy.data_ptr(), idx.data_ptr(),
                       idx.scalar_type() == at::kChar, dx.data_ptr(), N, H,
                       W, C, P, Q, kh, kw, sh, sw, ph, pw, cur_stream());
+}
+
+// dy, idx, top: [N,P,Q,C]; dx: [N,H,W,C]; blocks 0 = auto
+void py_maxpool_bwd8_relu_db(Tensor dy, Tensor idx, Tensor top, Tensor dx,
+                             Tensor db, int64_t N, int64_t H, int64_t W,
+                             int64_t C, int64_t P, int64_t Q, int64_t kh,
+                             int64_t kw, int64_t sh, int64_t sw, int64_t ph,
+                             int64_t pw, int64_t blocks) {
+  CHECK_CUDA(dy); CHECK_BF16(dy); CHECK_BF16(top); CHECK_BF16(dx);
+  CHECK_F32(db);
+  TORCH_CHECK(idx.scalar_type() == at::kChar, "int8 argmax only");
+  TORCH_CHECK(C > 0 && C % 8 == 0 && C <= 8192, "needs C % 8 == 0, <= 8192");
+  int64_t npq = N * P * Q * C, nhw = N * H * W * C;
+  TORCH_CHECK(dy.numel() == npq && idx.numel() == npq &&
+              top.numel() == npq && dx.numel() == nhw && db.numel() >= C,
+              "maxpool_bwd8_relu_db: tensor sizes do not match the geometry");
+  TORCH_CHECK(nhw / 8 < (int64_t(1) << 32), "activation too large");
+  TORCH_CHECK(blocks >= 0 && blocks <= 65535, "blocks");
+  cosamd::maxpool_bwd8_relu_db(dy.data_ptr(), idx.data_ptr(), top.data_ptr(),
+                               dx.data_ptr(), db.data_ptr<float>(), N, H, W,
+                               C, P, Q, kh, kw, sh, sw, ph, pw, (int)blocks,
+                               cur_stream());
 }
 
 void py_avgpool_fwd(Tensor x, Tensor y, int64_t N, int64_t H, int64_t W,
@@ -897,6 +945,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("im2col_f32", &py_im2col_f32);
   m.def("col2im_f32", &py_col2im_f32);
   m.def("relu_colsum_bwd", &py_relu_colsum_bwd);
+  m.def("relu_db_dense", &py_relu_db_dense);
   m.def("gemm_conv_fwd", &py_gemm_conv_fwd);
   m.def("gemm_conv_dw", &py_gemm_conv_dw);
   m.def("gemm_conv_fwd_sc", &py_gemm_conv_fwd_sc);
@@ -948,6 +997,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("col2im", &py_col2im);
   m.def("maxpool_fwd", &py_maxpool_fwd);
   m.def("maxpool_bwd", &py_maxpool_bwd);
+  m.def("maxpool_bwd8_relu_db", &py_maxpool_bwd8_relu_db);
   m.def("avgpool_fwd", &py_avgpool_fwd);
   m.def("avgpool_bwd", &py_avgpool_bwd);
   m.def("lrn_fwd", &py_lrn_fwd);

@@ -109,6 +109,87 @@ __global__ void maxpool_bwd8_kernel(
   }
 }
 
+// maxpool_bwd8 fused with the in-place ReLU (slope 0) below the pool and
+// the bias gradient of the conv below that:
+//   dx = bf16(sum of routed dy over windows whose pooled output is > 0),
+//   db[c] += column sums of the rounded dx.
+// Every window whose argmax is this pixel has top == y[pixel], so masking
+// the windows by top > 0 is exactly the ReLU's y > 0 mask, read from the
+// small pooled tensor at the offset idx and dy already use.  Same (p, q)
+// order and fp32 accumulation as maxpool_bwd8_kernel.  blockDim.x is a
+// multiple of C/8 (whole pixels per block), so the grid stride keeps a
+// thread on one channel octet and its 8 db partials stay in registers;
+// one LDS reduce and one atomic per (block, column).
+// (A variant that unrolled the 2x2 windows of a 3x3/stride-2 pool and
+// issued their 12 loads up front measured slower, 124 vs 107 us on pool1:
+// 79 VGPRs keep a second 1024-thread block off the CU.)
+__device__ __forceinline__ void pool_relu_acc(const i8x8& iv, const u16x8& dv,
+                                              const u16x8& tv, int rs,
+                                              float* acc) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    u16 traw = tv[j];
+    if ((int)iv[j] == rs &&
+        bf2f(*reinterpret_cast<const bf16*>(&traw)) > 0.f) {
+      u16 raw = dv[j];
+      acc[j] += bf2f(*reinterpret_cast<const bf16*>(&raw));
+    }
+  }
+}
+
+__global__ void __launch_bounds__(1024) maxpool_bwd8_relu_db_kernel(
+    const u16* __restrict__ dy, const signed char* __restrict__ idx,
+    const u16* __restrict__ top, u16* __restrict__ dx,
+    float* __restrict__ db,
+    int N, int H, int W, int C, int P, int Q,
+    int kh, int kw, int sh, int sw, int ph, int pw, int64_t total8) {
+  __shared__ float part[8192];           // blockDim.x * 8 <= 1024*8
+  int c8s = C / 8;
+  int cc = (threadIdx.x % c8s) * 8;
+  float dbacc[8] = {};
+  for (int64_t i8 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i8 < total8; i8 += (int64_t)gridDim.x * blockDim.x) {
+    unsigned iw = (unsigned)i8 / c8s;
+    int w = iw % W;
+    unsigned ih = iw / W;
+    int h = ih % H;
+    int n = ih / H;
+    float acc[8] = {};
+    int plo = max(0, (h + ph - kh + sh) / sh), phi = min(P - 1, (h + ph) / sh);
+    int qlo = max(0, (w + pw - kw + sw) / sw), qhi = min(Q - 1, (w + pw) / sw);
+    for (int p = plo; p <= phi; ++p) {
+      int rr = h - (p * sh - ph);
+      for (int q = qlo; q <= qhi; ++q) {
+        int rs = rr * kw + (w - (q * sw - pw));
+        int64_t o = (((int64_t)n * P + p) * Q + q) * C + cc;
+        i8x8 iv = *reinterpret_cast<const i8x8*>(idx + o);
+        u16x8 dv = *reinterpret_cast<const u16x8*>(dy + o);
+        u16x8 tv = *reinterpret_cast<const u16x8*>(top + o);
+        pool_relu_acc(iv, dv, tv, rs, acc);
+      }
+    }
+    u16x8 out;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      bf16 b = f2bf(acc[j]);
+      out[j] = *reinterpret_cast<u16*>(&b);
+      dbacc[j] += bf2f(b);
+    }
+    *reinterpret_cast<u16x8*>(
+        dx + (((int64_t)n * H + h) * W + w) * C + cc) = out;
+  }
+  // thread t = rg * c8s + octet, so part is [rg][C]
+#pragma unroll
+  for (int j = 0; j < 8; ++j) part[threadIdx.x * 8 + j] = dbacc[j];
+  __syncthreads();
+  int by = blockDim.x / c8s;
+  for (int col = threadIdx.x; col < C; col += blockDim.x) {
+    float sum = 0.f;
+    for (int g = 0; g < by; ++g) sum += part[g * C + col];
+    atomicAdd(db + col, sum);
+  }
+}
+
 template <typename IDX>
 __global__ void maxpool_fwd_kernel(
     const u16* __restrict__ x, u16* __restrict__ y, IDX* __restrict__ idx,
@@ -361,6 +442,25 @@ void maxpool_bwd(const void* dy, const void* idx, bool idx16, void* dx,
     maxpool_bwd_kernel<int><<<nblocks_for(total), 256, 0, stream>>>(
         (const u16*)dy, (const int*)idx, (u16*)dx, N, H, W, C, P, Q, kh,
         kw, sh, sw, ph, pw, total);
+}
+
+// C % 8 == 0, C <= 8192, int8 argmax (the caller checks).  Blocks of ~1024
+// threads: at the 2-per-CU block cap that is still 8 waves per SIMD for
+// this latency-bound gather.  blocks > 0 forces the grid (tests).
+void maxpool_bwd8_relu_db(const void* dy, const void* idx, const void* top,
+                          void* dx, float* db, int N, int H, int W, int C,
+                          int P, int Q, int kh, int kw, int sh, int sw,
+                          int ph, int pw, int blocks, hipStream_t stream) {
+  int c8s = C / 8;
+  int nthreads = 1024 - 1024 % c8s;      // whole pixels per block
+  int64_t total8 = (int64_t)N * H * W * c8s;
+  if (blocks <= 0)
+    blocks = (int)hmin<int64_t>(kFusedDbBlocks,
+                                (total8 + nthreads - 1) / nthreads);
+  blocks = hmax(1, blocks);
+  maxpool_bwd8_relu_db_kernel<<<blocks, nthreads, 0, stream>>>(
+      (const u16*)dy, (const signed char*)idx, (const u16*)top, (u16*)dx, db,
+      N, H, W, C, P, Q, kh, kw, sh, sw, ph, pw, total8);
 }
 
 void avgpool_fwd(const void* x, void* y, int N, int H, int W, int C,

@@ -1434,7 +1434,13 @@ def _cl_slice_ld(t):
     return None
 
 
-def relu_backward(y, dy, negative_slope=0.0, db_out=None):
+def relu_backward(y, dy, negative_slope=0.0, db_out=None, db_blocks=0):
+    """dx = relu'(y) * dy.  With db_out (a conv/fc bias-gradient slice to
+    accumulate into) returns (dx, done): done says the column sums of dx
+    were added to db_out in the same pass.  Dense channels-last / 2-D
+    tensors with C % 8 == 0 take relu_db_dense (db_blocks forces its row
+    block count, 0 = auto); channel windows and other C keep
+    relu_colsum_bwd."""
     ldy = _cl_slice_ld(y)
     if ldy is not None and y.dtype == torch.bfloat16:
         dy = dy if dy.dtype == torch.bfloat16 else dy.to(torch.bfloat16)
@@ -1449,6 +1455,12 @@ def relu_backward(y, dy, negative_slope=0.0, db_out=None):
         if db_out is not None and db_out.shape[0] == C:
             # fused: the producing conv's bias gradient accumulates into
             # its arena slice during this same pass (its colsum is skipped)
+            if C % 8 == 0 and ldy == C and lddy == C:
+                _ext.relu_db_dense(y.permute(0, 2, 3, 1),
+                                   dy.permute(0, 2, 3, 1),
+                                   dx.permute(0, 2, 3, 1), db_out,
+                                   negative_slope, N * H * W, C, db_blocks)
+                return dx, True
             _ext.relu_colsum_bwd(y, dy, dx.permute(0, 2, 3, 1), db_out,
                                  negative_slope, N * H * W, C, ldy, lddy)
             return dx, True
@@ -1459,7 +1471,12 @@ def relu_backward(y, dy, negative_slope=0.0, db_out=None):
     if db_out is not None and y.dim() == 2 and y.is_contiguous() \
             and db_out.shape[0] == y.shape[1]:
         dx = torch.empty_like(y)
-        _ext.relu_colsum_bwd(y, dy.reshape(y.shape), dx, db_out,
+        dy = dy.reshape(y.shape)
+        if y.shape[1] % 8 == 0 and dy.is_contiguous():
+            _ext.relu_db_dense(y, dy, dx, db_out, negative_slope,
+                               y.shape[0], y.shape[1], db_blocks)
+            return dx, True
+        _ext.relu_colsum_bwd(y, dy, dx, db_out,
                              negative_slope, y.shape[0], y.shape[1],
                              y.shape[1], y.shape[1])
         return dx, True
@@ -1524,11 +1541,35 @@ def maxpool_forward(x, kernel, stride, pad):
     idt = torch.int8 if kh * kw < 128 else torch.int32
     idx = torch.empty((N, P, Q, C), dtype=idt, device=x.device)
     _ext.maxpool_fwd(xl, y, idx, N, H, W, C, P, Q, kh, kw, sh, sw, ph, pw)
-    return y, (idx, (kh, kw, sh, sw, ph, pw), (N, C, H, W))
+    # y rides along for maxpool_backward_relu_db (its ReLU mask)
+    return y, (idx, (kh, kw, sh, sw, ph, pw), (N, C, H, W), y)
+
+
+def maxpool_backward_relu_db(idx_pack, dy, db_out, blocks=0):
+    """MAX-pool backward fused with the in-place ReLU (slope 0) and the
+    bias gradient of the conv under the pool: returns dx already masked by
+    y > 0 and adds its column sums to db_out (pre-zeroed fp32 [C]).
+    Returns None (nothing written) when the shape has no fused kernel:
+    C % 8 != 0, an int32 argmax, or a non-bf16 dy.  blocks forces the
+    grid (0 = auto)."""
+    idx, (kh, kw, sh, sw, ph, pw), (N, C, H, W), top = idx_pack
+    if C % 8 != 0 or C > 8192 or idx.dtype != torch.int8 \
+            or dy.dtype != torch.bfloat16 or top.dtype != torch.bfloat16 \
+            or db_out is None or db_out.dtype != torch.float32 \
+            or db_out.shape[0] != C or not db_out.is_contiguous():
+        return None
+    P, Q = dy.shape[2], dy.shape[3]
+    if tuple(top.shape) != (N, C, P, Q):
+        return None
+    dx = torch.empty((N, C, H, W), dtype=dy.dtype, device=dy.device,
+                     memory_format=torch.channels_last)
+    _ext.maxpool_bwd8_relu_db(_cl(dy), idx, _cl(top), dx, db_out, N, H, W,
+                              C, P, Q, kh, kw, sh, sw, ph, pw, blocks)
+    return dx
 
 
 def maxpool_backward(x_shape, idx_pack, dy):
-    idx, (kh, kw, sh, sw, ph, pw), (N, C, H, W) = idx_pack
+    idx, (kh, kw, sh, sw, ph, pw), (N, C, H, W) = idx_pack[:3]
     P, Q = dy.shape[2], dy.shape[3]
     dx = torch.empty((N, C, H, W), dtype=dy.dtype, device=dy.device,
                     memory_format=torch.channels_last)

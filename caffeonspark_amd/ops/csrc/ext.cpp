@@ -31,7 +31,12 @@ void col2im_f32(const float* dcol, float* dx, int N, int H, int W, int P,
 void gemm_conv_fwd(const void* X, const void* B, void* C,
                    const float* bias, const void* zpage, int M, int N,
                    int K, int ldb, int ldc, bool relu, bool accum,
-                   const int* geom, hipStream_t stream);
+                   const int* geom, int groups, int gs_c, int gs_b,
+                   int gs_n, int cfg, int vec, hipStream_t stream);
+struct ConvCfg { int id, bm, bn, waves, depth; };
+ConvCfg conv_fwd_plan(int M, int N, int K);
+int conv_fwd_num_cfgs();
+ConvCfg conv_fwd_cfg(int id);
 void gemm_conv_dw(const void* A, const void* X, float* C,
                   const void* zpage, int M, int N, int K, int lda, int ldc,
                   int store_mode, int splitk, float alpha, float* db,
@@ -320,8 +325,11 @@ void py_gemm_conv_fwd(Tensor X, Tensor B, Tensor C,
                       c10::optional<Tensor> bias, Tensor zpage,
                       int64_t M, int64_t N, int64_t K, int64_t ldb,
                       int64_t ldc, bool relu, bool accum,
-                      std::vector<int64_t> geom) {
+                      std::vector<int64_t> geom, int64_t groups,
+                      int64_t gs_c, int64_t gs_b, int64_t gs_n,
+                      int64_t cfg, int64_t vec) {
   CHECK_CUDA(X); CHECK_BF16(X); CHECK_BF16(B); CHECK_BF16(C);
+  TORCH_CHECK(groups >= 1, "groups must be positive");
   const float* bptr = nullptr;
   if (bias.has_value()) {
     CHECK_F32(bias.value());
@@ -332,8 +340,25 @@ void py_gemm_conv_fwd(Tensor X, Tensor B, Tensor C,
   for (int i = 0; i < 14; ++i) g[i] = (int)geom[i];
   cosamd::gemm_conv_fwd(X.data_ptr(), B.data_ptr(), C.data_ptr(), bptr,
                         zpage.data_ptr(), (int)M, (int)N, (int)K,
-                        (int)ldb, (int)ldc, relu, accum, g,
+                        (int)ldb, (int)ldc, relu, accum, g, (int)groups,
+                        (int)gs_c, (int)gs_b, (int)gs_n, (int)cfg, (int)vec,
                         cur_stream());
+}
+
+// (BM, BN, waves, ring depth) gemm_conv_fwd picks for [M, N, K]
+std::vector<int64_t> py_conv_fwd_plan(int64_t M, int64_t N, int64_t K) {
+  cosamd::ConvCfg p = cosamd::conv_fwd_plan((int)M, (int)N, (int)K);
+  return {p.bm, p.bn, p.waves, p.depth};
+}
+
+// the same four numbers for every configuration id (the cfg argument)
+std::vector<std::vector<int64_t>> py_conv_fwd_cfgs() {
+  std::vector<std::vector<int64_t>> out;
+  for (int i = 0; i < cosamd::conv_fwd_num_cfgs(); ++i) {
+    cosamd::ConvCfg p = cosamd::conv_fwd_cfg(i);
+    out.push_back({p.bm, p.bn, p.waves, p.depth});
+  }
+  return out;
 }
 
 void py_gemm_conv_dw(Tensor A, Tensor X, Tensor C,
@@ -946,7 +971,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("col2im_f32", &py_col2im_f32);
   m.def("relu_colsum_bwd", &py_relu_colsum_bwd);
   m.def("relu_db_dense", &py_relu_db_dense);
-  m.def("gemm_conv_fwd", &py_gemm_conv_fwd);
+  // the 13 leading arguments are one group's GEMM; groups > 1 launches
+  // every group at once (strides: input channels, B rows, C columns)
+  m.def("gemm_conv_fwd", &py_gemm_conv_fwd, py::arg("X"), py::arg("B"),
+        py::arg("C"), py::arg("bias"), py::arg("zpage"), py::arg("M"),
+        py::arg("N"), py::arg("K"), py::arg("ldb"), py::arg("ldc"),
+        py::arg("relu"), py::arg("accum"), py::arg("geom"),
+        py::arg("groups") = 1, py::arg("gs_c") = 0, py::arg("gs_b") = 0,
+        py::arg("gs_n") = 0, py::arg("cfg") = -1, py::arg("vec") = -1);
+  m.def("conv_fwd_plan", &py_conv_fwd_plan);
+  m.def("conv_fwd_cfgs", &py_conv_fwd_cfgs);
   m.def("gemm_conv_dw", &py_gemm_conv_dw);
   m.def("gemm_conv_fwd_sc", &py_gemm_conv_fwd_sc);
   m.def("gemm_conv_dw_sc", &py_gemm_conv_dw_sc);

@@ -14,21 +14,40 @@
 //   decode_tile      blockIdx -> XCD-swizzled (bm, bn, tile_m, tile_n)
 //   stage_*          global -> LDS; the only part that differs per operand
 //   load_frags_mfma  LDS -> fragments -> 16x16x32 bf16 MFMA (fp32 acc)
+//   TileCfg          block tile x wave grid -> per-wave fragment and DMA counts
 //   pipelined_loop   counted-vmcnt K loop for the DMA-staged kernels
 //                    (gemm_conv_dw_tr_kernel has its own [k][col] image,
 //                    transposed fragment reads and ring; see there)
 //   epilogue_bf16    bias + ReLU + alpha, bf16 store or RMW accumulate
+//   epilogue_bf16_vec  the same through LDS with 16-byte accesses (conv)
 //   epilogue_f32     fp32 plain store or atomic add (split-K)
 //
 // Kernels, their staging policies, and who launches them:
 //   gemm_kernel<TA, TB, STORE_MODE, WAVES>       gemm_bf16[_batched]
-//     128x128 tile; interior aligned NN tiles run pipelined_loop<WAVES, 2>
+//     128x128 tile; interior aligned NN tiles run pipelined_loop at depth 2
 //     with ADirect (direct-to-LDS DMA), everything else a guarded loop.
 //     All 16 TAxTBxSTORE_MODE combinations at WAVES=4, NN also at WAVES=8.
-//   gemm_conv_fwd_kernel<WAVES, DEPTH>           gemm_conv_fwd
-//     pipelined_loop<WAVES, DEPTH> with AImplicit (im2col gather DMA).
-//     <8,4> (one barrier per tile) when w8 and 4*BK <= K <= COS_CONVQ,
-//     else <8,2> when w8, else <4,2>.
+//   gemm_conv_fwd_kernel<TileCfg, DEPTH>         gemm_conv_fwd
+//     pipelined_loop with AImplicit (im2col gather DMA) on a block tile
+//     chosen per launch by conv_fwd_plan (COS_CONV_CFGS lists every
+//     instantiation).  N tile: the one of 48/64/96/128 columns with the
+//     least padding, the wider on a tie; COS_CONV_BN=48/64/96/128 forces
+//     one (0/unset: automatic); unlike COS_CONVQ it is read on every
+//     call, because the tests flip it under conv2d_forward/backward, which
+//     take no tile argument.  128 columns keep the fixed-tile rule:
+//     8 waves, depth 4 (one barrier per tile) when w8 and 4*BK <= K <=
+//     COS_CONVQ, else 8 waves depth 2 when w8, else 4 waves.  Narrower
+//     tiles take rows, waves and depth from the sweep in
+//     profiles/alexnet_1gpu_conv_tiles.md (256-row blocks for 48 and 64
+//     columns at large M).  All widths give bit-identical results.
+//     A grouped convolution is one launch: blockIdx.y is the group, and
+//     three strides move the input channel window, the B rows and the C
+//     columns per group (bias advances by N).
+//     Epilogue: epilogue_bf16_vec (accumulators transposed through the
+//     freed LDS, 16-byte stores / read-add-write, float4 bias) when N, ldc
+//     and the group's column offset are multiples of 8 and C and bias are
+//     16-byte aligned; the element-wise epilogue_bf16 otherwise.  Both
+//     store the same bits.
 //   gemm_conv_fwd_sc_kernel<WAVES>               gemm_conv_fwd_sc
 //     small-C gather through registers, own __syncthreads loop; <8>/<4>.
 //   gemm_wide_tt_kernel<STORE, BStage>           launch_wide_tt
@@ -80,16 +99,16 @@ __device__ __forceinline__ int swz_chunk(int row, int chunk) {
 
 struct Tile { int bm, bn, tile_m, tile_n; };
 
-// XCD-aware block swizzle -> output tile of a BM x TBN tiling
-template <int TBN>
+// XCD-aware block swizzle -> output tile of a TBM x TBN tiling
+template <int TBN, int TBM = BM>
 __device__ __forceinline__ Tile decode_tile(int M, int N) {
-  int mblocks = (M + BM - 1) / BM;
+  int mblocks = (M + TBM - 1) / TBM;
   int nblocks = (N + TBN - 1) / TBN;
   int bid = xcd_swizzle(blockIdx.x, mblocks * nblocks);
   Tile t;
   t.bm = bid / nblocks;
   t.bn = bid % nblocks;
-  t.tile_m = t.bm * BM;
+  t.tile_m = t.bm * TBM;
   t.tile_n = t.bn * TBN;
   return t;
 }
@@ -99,19 +118,45 @@ __device__ __forceinline__ Tile decode_tile(int M, int N) {
 constexpr int mrows_of(int waves) { return BM / (waves / 2); }
 constexpr int mfrags_of(int waves) { return mrows_of(waves) / 16; }
 
-// One K-tile of compute for a wave: MF x 4 fragments (wave tile
-// MROWS x 64 at (wm, wn)) from the canonical swizzled LDS layout, then
-// the MF x 4 MFMA block.  PRIO brackets the MFMAs with s_setprio for the
+// Block tile TBM x TBN x BK on a WM x WN wave grid: each wave owns
+// MROWS x NCOLS outputs as MF x NF 16x16 fragments.  An operand tile is
+// staged in 1 KB chunks (16 rows of BK), one DMA wave-instruction each;
+// every wave issues the same A_CPW + B_CPW of them per tile so that the
+// pipelined loop's counted wait is one literal.  Where the B tile's
+// chunks (3 for 48 rows, 6 for 96) do not divide over the waves, the LDS
+// image is rounded up to B_CPW * WAVES chunks and the surplus instructions
+// fetch the zero page into the unread tail.
+template <int TBM_, int TBN_, int WM_, int WN_>
+struct TileCfg {
+  static constexpr int TBM = TBM_, TBN = TBN_, WM = WM_, WN = WN_;
+  static constexpr int WAVES = WM * WN;
+  static constexpr int MROWS = TBM / WM, NCOLS = TBN / WN;
+  static constexpr int MF = MROWS / 16, NF = NCOLS / 16;
+  static constexpr int A_CHUNKS = TBM / 16, B_CHUNKS = TBN / 16;
+  static constexpr int A_CPW = A_CHUNKS / WAVES;
+  static constexpr int B_CPW = (B_CHUNKS + WAVES - 1) / WAVES;
+  static constexpr int A_ELEMS = TBM * BK;
+  static constexpr int B_ELEMS = B_CPW * WAVES * 512;
+  static_assert(MROWS % 16 == 0 && NCOLS % 16 == 0, "whole fragments");
+  static_assert(A_CHUNKS % WAVES == 0, "A chunks divide over the waves");
+};
+// the 128x128 tile of gemm_kernel and the fixed-tile conv kernels
+template <int WAVES>
+using Tile128 = TileCfg<BM, BN, WAVES / 2, 2>;
+
+// One K-tile of compute for a wave: MF + NF fragments (wave tile
+// MROWS x NCOLS at (wm, wn)) from the canonical swizzled LDS layout, then
+// the MF x NF MFMA block.  PRIO brackets the MFMAs with s_setprio for the
 // pipelined loops, where other waves are issuing DMA at the same time.
-template <int MF, int MROWS, bool PRIO>
+template <int MF, int MROWS, bool PRIO, int NF = 4, int NCOLS = 64>
 __device__ __forceinline__ void load_frags_mfma(
     const bf16* As, const bf16* Bs, int wm, int wn, int lane,
-    f32x4 (&acc)[MF][4]) {
+    f32x4 (&acc)[MF][NF]) {
   int lrow = lane & 15, lchunk = lane >> 4;
-  bf16x8 afrag[MF], bfrag[4];
+  bf16x8 afrag[MF], bfrag[NF];
 #pragma unroll
-  for (int f = 0; f < 4; ++f) {
-    int rb = wn * 64 + f * 16 + lrow;
+  for (int f = 0; f < NF; ++f) {
+    int rb = wn * NCOLS + f * 16 + lrow;
     bfrag[f] = *reinterpret_cast<const bf16x8*>(
         Bs + rb * BK + (swz_chunk(rb, lchunk) << 3));
   }
@@ -125,7 +170,7 @@ __device__ __forceinline__ void load_frags_mfma(
 #pragma unroll
   for (int fm = 0; fm < MF; ++fm)
 #pragma unroll
-    for (int fn = 0; fn < 4; ++fn)
+    for (int fn = 0; fn < NF; ++fn)
       acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
           afrag[fm], bfrag[fn], acc[fm][fn], 0, 0, 0);
   if (PRIO) __builtin_amdgcn_s_setprio(0);
@@ -136,17 +181,17 @@ __device__ __forceinline__ void load_frags_mfma(
 // exclusive tiles and a single split make the plain RMW race-free.
 // Accum is bool for a runtime choice, or std::true_type/false_type so
 // the unused branch never reaches the optimizer.
-template <int MF, int MROWS, class Accum>
+template <int MF, int MROWS, int NF = 4, int NCOLS = 64, class Accum>
 __device__ __forceinline__ void epilogue_bf16(
-    const f32x4 (&acc)[MF][4], bf16* C, const float* bias, int M, int N,
+    const f32x4 (&acc)[MF][NF], bf16* C, const float* bias, int M, int N,
     int ldc, int tile_m, int tile_n, int wm, int wn, int lane, int relu,
     float alpha, Accum accum) {
   int crow0 = tile_m + wm * MROWS + ((lane >> 4) << 2);
-  int ccol0 = tile_n + wn * 64 + (lane & 15);
+  int ccol0 = tile_n + wn * NCOLS + (lane & 15);
 #pragma unroll
   for (int fm = 0; fm < MF; ++fm) {
 #pragma unroll
-    for (int fn = 0; fn < 4; ++fn) {
+    for (int fn = 0; fn < NF; ++fn) {
       int col = ccol0 + fn * 16;
       if (col >= N) continue;
       float badd = (bias != nullptr) ? bias[col] : 0.f;
@@ -161,6 +206,79 @@ __device__ __forceinline__ void epilogue_bf16(
         C[off] = f2bf(v);
       }
     }
+  }
+}
+
+// 16-byte form of epilogue_bf16 for the conv kernel (alpha = 1): each wave
+// transposes its accumulators, one 16-row fragment band at a time, through
+// a private LDS slab so that a lane holds 8 consecutive channels of one
+// output row; bias comes as two float4, the store (and the accumulating
+// read-add-write) is one 16-byte access.  Same floats, same order of bias,
+// ReLU, accumulate and rounding as the element-wise form.  The caller
+// guarantees N, ldc and the column offset are multiples of 8 and C and
+// bias 16-byte aligned, and that nothing else uses `lds` any more.
+// The slab's row stride of NCOLS + 4 floats puts the four row groups a
+// wave-instruction writes (rows r, r+4, r+8, r+12) on alternating halves
+// of the 32 banks: 2-way, the minimum for 256 bytes.
+template <class Cfg>
+constexpr int vec_slab_floats() { return Cfg::WAVES * 16 * (Cfg::NCOLS + 4); }
+
+template <class Cfg>
+__device__ __forceinline__ void epilogue_bf16_vec(
+    const f32x4 (&acc)[Cfg::MF][Cfg::NF], float* lds, bf16* C,
+    const float* bias, int M, int N, int ldc, int tile_m, int tile_n, int wm,
+    int wn, int wave, int lane, int relu, int accum) {
+  constexpr int LD = Cfg::NCOLS + 4;
+  constexpr int GPR = Cfg::NCOLS / 8;        // 8-column groups per row
+  constexpr int TASKS = 16 * GPR;            // (row, group) pairs per band
+  float* slab = lds + wave * 16 * LD;
+  int wr = (lane >> 4) << 2, wc = lane & 15;
+#pragma unroll
+  for (int fm = 0; fm < Cfg::MF; ++fm) {
+#pragma unroll
+    for (int fn = 0; fn < Cfg::NF; ++fn)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        slab[(wr + r) * LD + fn * 16 + wc] = acc[fm][fn][r];
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int t0 = 0; t0 < TASKS; t0 += 64) {
+      int t = t0 + lane;
+      int row = t / GPR, cg = t - row * GPR;
+      int grow = tile_m + wm * Cfg::MROWS + fm * 16 + row;
+      int col = tile_n + wn * Cfg::NCOLS + cg * 8;
+      if ((TASKS % 64 == 0 || t < TASKS) && grow < M && col < N) {
+        f32x4 lo = *reinterpret_cast<const f32x4*>(slab + row * LD + cg * 8);
+        f32x4 hi =
+            *reinterpret_cast<const f32x4*>(slab + row * LD + cg * 8 + 4);
+        float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        if (bias != nullptr) {
+          f32x4 b0 = *reinterpret_cast<const f32x4*>(bias + col);
+          f32x4 b1 = *reinterpret_cast<const f32x4*>(bias + col + 4);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { v[j] += b0[j]; v[4 + j] += b1[j]; }
+        }
+        if (relu) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[j] = v[j] < 0.f ? 0.f : v[j];
+        }
+        short8v* dst =
+            reinterpret_cast<short8v*>(C + (int64_t)grow * ldc + col);
+        bf16 o[8];
+        if (accum) {
+          short8v old = *dst;
+          __builtin_memcpy(o, &old, 16);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[j] += bf2f(o[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = f2bf(v[j]);
+        short8v out;
+        __builtin_memcpy(&out, o, 16);
+        *dst = out;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
   }
 }
 
@@ -288,20 +406,25 @@ __device__ __forceinline__ void stage_trans_pair_guarded(
   }
 }
 
-// fast path: interior tile, aligned — direct-to-LDS DMA, 16 B per lane.
-template <int WAVES = 4>
+// CHUNKS 1 KB chunks (16 rows each) over WAVES waves.  With a zpage, a
+// chunk past CHUNKS (TileCfg's surplus) or past the operand's `rows`
+// still issues its instruction, from the zero page.
+template <int WAVES = 4, int CHUNKS = 8>
 __device__ __forceinline__ void stage_direct_fast(
-    bf16* lds, const bf16* g, int row0, int ld, int k0, int tid) {
+    bf16* lds, const bf16* g, int row0, int ld, int k0, int tid,
+    const bf16* zpage = nullptr, int rows = 0) {
   int wave = tid >> 6, lane = tid & 63;
-  constexpr int CPW = 8 / WAVES;         // chunks per wave
+  constexpr int CPW = (CHUNKS + WAVES - 1) / WAVES;  // chunks per wave
 #pragma unroll
   for (int it = 0; it < CPW; ++it) {
-    int chunk = wave * CPW + it;         // 8 chunks of 512 elements
+    int chunk = wave * CPW + it;         // chunks of 512 elements
     int idx = chunk * 512 + lane * 8;    // linear element index in tile
     int row = idx >> 5;                  // /32
     int kk = swz_chunk(row, (idx & 31) >> 3) << 3;  // pre-swizzled source
-    auto* gp = (const __attribute__((address_space(1))) unsigned int*)(
-        g + (int64_t)(row0 + row) * ld + k0 + kk);
+    const bf16* src = g + (int64_t)(row0 + row) * ld + k0 + kk;
+    if (zpage != nullptr && (chunk >= CHUNKS || row0 + row >= rows))
+      src = zpage;
+    auto* gp = (const __attribute__((address_space(1))) unsigned int*)src;
     auto* lp = (__attribute__((address_space(3))) unsigned int*)(
         lds + chunk * 512);
     __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
@@ -358,13 +481,13 @@ __device__ __forceinline__ void decode_rows(int* rinfo, const CGeom& gm,
 // issues, so the pipeline's counted s_waitcnt vmcnt(N) stays exact (a
 // divergent skip would desynchronize the count), and no LDS zero-fill
 // writes are needed.
-template <int WAVES>
+template <int WAVES, int CHUNKS = 8>
 __device__ __forceinline__ void stage_implicit_fast(
     bf16* lds_, const bf16* X, const bf16* zpage, const CGeom& gm,
     const int* rinfo, int k0, int tid) {
   auto* lds = reinterpret_cast<unsigned short*>(lds_);
   int wave = tid >> 6, lane = tid & 63;
-  constexpr int CPW = 8 / WAVES;
+  constexpr int CPW = CHUNKS / WAVES;
 #pragma unroll
   for (int it = 0; it < CPW; ++it) {
     int chunk = wave * CPW + it;
@@ -664,16 +787,15 @@ __global__ __launch_bounds__(WNT, 1) void gemm_wide_tt_kernel(
 //   DEPTH=4: one barrier per tile — the buffer written at iter t+1 (slot
 //     (t+3)&3) was last read at iter t-1, and barrier_t separates them.
 //     65.5 KB of LDS, still 2 blocks/CU within CDNA4's 160 KB.
-// Needs k_end - k_begin to be a multiple of BK and at least two tiles:
-// with a single tile nothing is prefetched, fewer than N loads are ever
-// outstanding, and the counted wait would pass before the tile landed.
+// Needs k_end - k_begin to be a multiple of BK and at least PF tiles (the
+// hosts pad to two): the prologue and the tail assume PF tiles exist.
 
 struct ADirect {          // [rows][K] matrix
   const bf16* A;
   int row0, ld;
-  template <int WAVES>
+  template <int WAVES, int CHUNKS>
   __device__ __forceinline__ void stage(bf16* lds, int k0, int tid) const {
-    stage_direct_fast<WAVES>(lds, A, row0, ld, k0, tid);
+    stage_direct_fast<WAVES, CHUNKS>(lds, A, row0, ld, k0, tid);
   }
 };
 
@@ -682,9 +804,9 @@ struct AImplicit {        // im2col gather from the NHWC input
   const bf16* zpage;
   const CGeom& gm;
   const int* rinfo;
-  template <int WAVES>
+  template <int WAVES, int CHUNKS>
   __device__ __forceinline__ void stage(bf16* lds, int k0, int tid) const {
-    stage_implicit_fast<WAVES>(lds, X, zpage, gm, rinfo, k0, tid);
+    stage_implicit_fast<WAVES, CHUNKS>(lds, X, zpage, gm, rinfo, k0, tid);
   }
 };
 
@@ -693,39 +815,59 @@ __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-template <int WAVES, int DEPTH, class AStage>
+// Asb / Bsb: the ring's DEPTH stages of Cfg::A_ELEMS / Cfg::B_ELEMS each.
+// zpage / b_rows: stage_direct_fast's guard for B (nullptr: none).
+template <class Cfg, int DEPTH, class AStage>
 __device__ __forceinline__ void pipelined_loop(
-    bf16 (*Asb)[BM * BK], bf16 (*Bsb)[BN * BK], const AStage& astage,
-    const bf16* B, int tile_n, int ldb, int k_begin, int k_end, int tid,
-    int wm, int wn, int lane, f32x4 (&acc)[mfrags_of(WAVES)][4]) {
+    bf16* Asb, bf16* Bsb, const AStage& astage, const bf16* B,
+    const bf16* zpage, int b_rows, int tile_n, int ldb, int k_begin,
+    int k_end, int tid, int wm, int wn, int lane,
+    f32x4 (&acc)[Cfg::MF][Cfg::NF]) {
+  constexpr int WAVES = Cfg::WAVES;
   constexpr int PF = DEPTH / 2;              // tiles in flight ahead
-  // each wave issues 8/WAVES DMA loads per operand per tile; the PF
-  // prefetched tiles' loads stay outstanding while the current tile's
-  // are waited for
-  constexpr int VMCNT = PF * 2 * (8 / WAVES);
+  // each wave issues A_CPW + B_CPW DMA loads per tile; the PF prefetched
+  // tiles' loads stay outstanding while the current tile's are waited for
+  constexpr int VMCNT = PF * (Cfg::A_CPW + Cfg::B_CPW);
 #pragma unroll
   for (int p = 0; p < PF; ++p)
     if (p == 0 || k_begin + p * BK < k_end) {
-      astage.template stage<WAVES>(Asb[p], k_begin + p * BK, tid);
-      stage_direct_fast<WAVES>(Bsb[p], B, tile_n, ldb, k_begin + p * BK,
-                               tid);
+      astage.template stage<WAVES, Cfg::A_CHUNKS>(
+          Asb + p * Cfg::A_ELEMS, k_begin + p * BK, tid);
+      stage_direct_fast<WAVES, Cfg::B_CHUNKS>(
+          Bsb + p * Cfg::B_ELEMS, B, tile_n, ldb, k_begin + p * BK, tid,
+          zpage, b_rows);
     }
   int cur = 0;                               // ring slot of tile k0
-  for (int k0 = k_begin; k0 < k_end; k0 += BK) {
-    if (k0 + PF * BK < k_end) {
-      int nxt = (cur + PF) & (DEPTH - 1);
-      astage.template stage<WAVES>(Asb[nxt], k0 + PF * BK, tid);
-      stage_direct_fast<WAVES>(Bsb[nxt], B, tile_n, ldb, k0 + PF * BK,
-                               tid);
-    }
-    wait_vmcnt<VMCNT>();
+  auto compute = [&](int slot) {
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
-    load_frags_mfma<mfrags_of(WAVES), mrows_of(WAVES), true>(
-        Asb[cur], Bsb[cur], wm, wn, lane, acc);
+    load_frags_mfma<Cfg::MF, Cfg::MROWS, true, Cfg::NF, Cfg::NCOLS>(
+        Asb + slot * Cfg::A_ELEMS, Bsb + slot * Cfg::B_ELEMS, wm, wn, lane,
+        acc);
+  };
+  int k0 = k_begin;
+  for (; k0 + PF * BK < k_end; k0 += BK) {
+    int nxt = (cur + PF) & (DEPTH - 1);
+    astage.template stage<WAVES, Cfg::A_CHUNKS>(
+        Asb + nxt * Cfg::A_ELEMS, k0 + PF * BK, tid);
+    stage_direct_fast<WAVES, Cfg::B_CHUNKS>(
+        Bsb + nxt * Cfg::B_ELEMS, B, tile_n, ldb, k0 + PF * BK, tid, zpage,
+        b_rows);
+    wait_vmcnt<VMCNT>();
+    compute(cur);
     if (DEPTH == 2) __builtin_amdgcn_s_barrier();
     cur = (cur + 1) & (DEPTH - 1);
   }
+  // the last PF tiles: nothing more is issued, so fewer loads stay in
+  // flight behind the awaited tile and the count shrinks with them
+  static_assert(PF == 1 || PF == 2, "tail waits written out for PF <= 2");
+  if (PF == 2) {
+    wait_vmcnt<VMCNT / 2>();
+    compute(cur);
+    cur = (cur + 1) & (DEPTH - 1);
+  }
+  wait_vmcnt<0>();
+  compute(cur);
 }
 
 // ------------------------------------------------------------------ kernel
@@ -772,8 +914,9 @@ __global__ __launch_bounds__(WAVES * 64, 2) void gemm_kernel(
                 ((k_end - k_begin) % BK == 0) && (k_begin % 8 == 0);
 
   if (a_fast && b_fast && (k_end - k_begin) >= 2 * BK) {
-    pipelined_loop<WAVES, 2>(Asb, Bsb, ADirect{A, tile_m, lda}, B, tile_n,
-                             ldb, k_begin, k_end, tid, wm, wn, lane, acc);
+    pipelined_loop<Tile128<WAVES>, 2>(
+        &Asb[0][0], &Bsb[0][0], ADirect{A, tile_m, lda}, B, nullptr, 0,
+        tile_n, ldb, k_begin, k_end, tid, wm, wn, lane, acc);
   } else {
     bf16* As = Asb[0];
     bf16* Bs = Bsb[0];
@@ -816,31 +959,66 @@ __global__ __launch_bounds__(WAVES * 64, 2) void gemm_kernel(
 // Always the pipelined loop: the implicit A staging zero-fills
 // k >= Kcol, so K runs over Kpad (32-aligned by the host) with no
 // guarded edge cases, and Wr's padded rows/columns are zero.
-template <int WAVES, int DEPTH>
-__global__ __launch_bounds__(WAVES * 64, 2) void gemm_conv_fwd_kernel(
+//
+// Cfg is the block tile (TileCfg): N tiles of 48, 64, 96 and 128 columns
+// so that a layer's output width is padded to 16, not to 128.  The k
+// order of every output element is the same in all of them (one
+// 16x16x32 MFMA per K tile, ascending), so they agree bit for bit.
+//
+// blockIdx.y is the group of a grouped convolution: group g reads input
+// channels from c0 + g*gs_c, B rows from g*gs_b, bias from g*N, and
+// writes C columns from g*gs_n — one launch where the host used to loop.
+//
+// One __shared__ object for ring and rinfo: a second object beside a
+// DMA-staged array can make the compiler drain vmcnt before LDS reads.
+template <class Cfg, int DEPTH>
+__global__ __launch_bounds__(Cfg::WAVES * 64, 2) void gemm_conv_fwd_kernel(
     const bf16* __restrict__ X, const bf16* __restrict__ B,
     bf16* __restrict__ C, const float* __restrict__ bias,
     const bf16* __restrict__ zpage,
     int M, int N, int K, int ldb, int ldc, int relu, int accum,
-    CGeom gm) {
-  __shared__ bf16 Asb[DEPTH][BM * BK];
-  __shared__ bf16 Bsb[DEPTH][BN * BK];
-  __shared__ int rinfo[BM * 3];
+    CGeom gm, int gs_c, int gs_b, int gs_n, int vec) {
+  // B holds pad128(N) rows per group (zero beyond N); a forced narrow
+  // tile can round N up past that, and those rows come from zpage
+  int b_rows = (N + 127) / 128 * 128;
+  constexpr int RING = DEPTH * (Cfg::A_ELEMS + Cfg::B_ELEMS);
+  constexpr int STAGING = RING + Cfg::TBM * 3 * (sizeof(int) / sizeof(bf16));
+  // the vector epilogue's slabs reuse the ring (and rinfo) after the loop
+  constexpr int SLABS = vec_slab_floats<Cfg>() * (sizeof(float) / sizeof(bf16));
+  __shared__ __attribute__((aligned(16)))
+  bf16 smem[STAGING > SLABS ? STAGING : SLABS];
+  bf16* Asb = smem;
+  bf16* Bsb = smem + DEPTH * Cfg::A_ELEMS;
+  int* rinfo = reinterpret_cast<int*>(smem + RING);
 
-  Tile t = decode_tile<BN>(M, N);
+  int g = blockIdx.y;
+  gm.c0 += g * gs_c;
+  B += (int64_t)g * gs_b * ldb;
+  C += g * gs_n;
+  if (bias != nullptr) bias += g * N;
+
+  Tile t = decode_tile<Cfg::TBN, Cfg::TBM>(M, N);
   int tid = threadIdx.x;
   int wave = tid >> 6, lane = tid & 63;
-  int wm = wave >> 1, wn = wave & 1;
+  int wm = wave / Cfg::WN, wn = wave % Cfg::WN;
 
-  decode_rows(rinfo, gm, t.tile_m, M, BM, tid);
+  decode_rows(rinfo, gm, t.tile_m, M, Cfg::TBM, tid);
   __syncthreads();
 
-  f32x4 acc[mfrags_of(WAVES)][4] = {};
-  pipelined_loop<WAVES, DEPTH>(Asb, Bsb, AImplicit{X, zpage, gm, rinfo}, B,
-                               t.tile_n, ldb, 0, K, tid, wm, wn, lane, acc);
-  epilogue_bf16<mfrags_of(WAVES), mrows_of(WAVES)>(
-      acc, C, bias, M, N, ldc, t.tile_m, t.tile_n, wm, wn, lane, relu, 1.f,
-      accum != 0);
+  f32x4 acc[Cfg::MF][Cfg::NF] = {};
+  pipelined_loop<Cfg, DEPTH>(Asb, Bsb, AImplicit{X, zpage, gm, rinfo}, B,
+                             zpage, b_rows, t.tile_n, ldb, 0, K, tid, wm,
+                             wn, lane, acc);
+  if (vec) {
+    __syncthreads();                 // every wave is done reading the ring
+    epilogue_bf16_vec<Cfg>(acc, reinterpret_cast<float*>(smem), C, bias, M,
+                           N, ldc, t.tile_m, t.tile_n, wm, wn, wave, lane,
+                           relu, accum);
+  } else {
+    epilogue_bf16<Cfg::MF, Cfg::MROWS, Cfg::NF, Cfg::NCOLS>(
+        acc, C, bias, M, N, ldc, t.tile_m, t.tile_n, wm, wn, lane, relu,
+        1.f, accum != 0);
+  }
 }
 
 // small-C forward conv GEMM: double-buffered __syncthreads pipeline
@@ -1236,14 +1414,78 @@ static CGeom make_geom(const int* g) {
   return gm;
 }
 
-void gemm_conv_fwd(const void* X, const void* B, void* C,
-                   const float* bias, const void* zpage, int M, int N,
-                   int K, int ldb, int ldc, bool relu, bool accum,
-                   const int* geom, hipStream_t stream) {
-  CGeom gm = make_geom(geom);
-  int mblocks = (M + BM - 1) / BM, nblocks = (N + BN - 1) / BN;
-  dim3 grid(mblocks * nblocks);
-  bool w8 = use_w8(M, N);
+// Every instantiation of gemm_conv_fwd_kernel: CFG_(id, TBM, TBN, WM, WN,
+// DEPTH).  The ids are what gemm_conv_fwd's cfg argument and
+// tools/conv_tile_bench.py name; 0-2 are the fixed 128-wide kernels
+// <8,4>, <8,2> and <4,2>.  Ids 12-17 lost the sweep everywhere
+// (profiles/alexnet_1gpu_conv_tiles.md); they are compiled only with
+// -DCOS_CONV_SWEEP, to repeat it.
+#ifdef COS_CONV_SWEEP
+#define COS_CONV_SWEEP_CFGS(CFG_)                                           \
+  CFG_(12, 128, 96, 4, 2, 4)  CFG_(13, 256, 96, 4, 2, 2)                    \
+  CFG_(14, 256, 64, 4, 1, 2)  CFG_(15, 256, 48, 4, 1, 2)                    \
+  CFG_(16, 128, 96, 2, 2, 4)  CFG_(17, 128, 64, 2, 2, 4)
+#else
+#define COS_CONV_SWEEP_CFGS(CFG_)
+#endif
+#define COS_CONV_CFGS(CFG_)                                                 \
+  CFG_(0, 128, 128, 4, 2, 4)  CFG_(1, 128, 128, 4, 2, 2)                    \
+  CFG_(2, 128, 128, 2, 2, 2)  CFG_(3, 128, 96, 2, 2, 2)                     \
+  CFG_(4, 128, 96, 4, 2, 2)   CFG_(5, 128, 64, 2, 2, 2)                     \
+  CFG_(6, 128, 64, 4, 2, 2)   CFG_(7, 128, 64, 4, 2, 4)                     \
+  CFG_(8, 256, 64, 4, 2, 2)   CFG_(9, 128, 48, 4, 1, 2)                     \
+  CFG_(10, 128, 48, 4, 1, 4)  CFG_(11, 256, 48, 8, 1, 2)                    \
+  COS_CONV_SWEEP_CFGS(CFG_)
+
+struct ConvCfg { int id, bm, bn, waves, depth; };
+
+static const ConvCfg kConvCfgs[] = {
+#define CFG_(ID, TBM, TBN, WM, WN, DEPTH) {ID, TBM, TBN, WM * WN, DEPTH},
+    COS_CONV_CFGS(CFG_)
+#undef CFG_
+};
+constexpr int kNumConvCfgs = sizeof(kConvCfgs) / sizeof(kConvCfgs[0]);
+
+// Which instantiations take the 16-byte epilogue when the operands allow
+// it.  Measured per tile and shape against the element-wise one ("The
+// 16-byte epilogue" in the same profile) it was 1-22 % faster for every
+// tile at every shape, so none is excluded; a tile that loses gets its
+// id listed here.
+static bool conv_vec(int id) {
+  (void)id;
+  return true;
+}
+
+int conv_fwd_num_cfgs() { return kNumConvCfgs; }
+ConvCfg conv_fwd_cfg(int id) {
+  if (id < 0 || id >= kNumConvCfgs)
+    throw std::runtime_error("conv_fwd_cfg: no such configuration");
+  return kConvCfgs[id];
+}
+
+// N tile with the least padding, ceil(N/BN)*BN minimal, the wider on a
+// tie; COS_CONV_BN = 48/64/96/128 forces one (0 or unset: automatic).
+static int conv_bn(int N) {
+  // read per call, unlike COS_CONVQ: conv2d_forward/backward take no tile
+  // argument, and the tests flip the width under them inside one process
+  const char* e = getenv("COS_CONV_BN");
+  int forced = e ? atoi(e) : 0;
+  if (forced != 0 && forced != 48 && forced != 64 && forced != 96 &&
+      forced != 128)
+    throw std::runtime_error("COS_CONV_BN must be 0, 48, 64, 96 or 128");
+  if (forced) return forced;
+  int best = 128, best_pad = (N + 127) / 128 * 128;
+  for (int bn : {96, 64, 48}) {
+    int pad = (N + bn - 1) / bn * bn;
+    if (pad < best_pad) { best = bn; best_pad = pad; }
+  }
+  return best;
+}
+
+// The configuration gemm_conv_fwd runs [M, N, K] with (N per group).
+// BN = 128 is the fixed-tile rule: 8 waves for skinny shapes (use_w8),
+// the one-barrier depth-4 ring inside the COS_CONVQ K gate.
+ConvCfg conv_fwd_plan(int M, int N, int K) {
   static const int quad = [] {
     // COS_CONVQ: 0 = off, otherwise a max-K gate (1 = "all shapes").
     // Default 1152: same-box A/B is +2.2% CIFAR, neutral AlexNet/
@@ -1253,14 +1495,59 @@ void gemm_conv_fwd(const void* X, const void* B, void* C,
     int v = atoi(e);
     return v == 1 ? 1 << 30 : v;
   }();
-#define COS_CONV_FWD(WAVES, DEPTH)                                          \
-  gemm_conv_fwd_kernel<WAVES, DEPTH><<<grid, WAVES * 64, 0, stream>>>(      \
-      (const bf16*)X, (const bf16*)B, (bf16*)C, bias, (const bf16*)zpage,   \
-      M, N, K, ldb, ldc, relu ? 1 : 0, accum ? 1 : 0, gm)
-  if (quad && w8 && K >= 4 * BK && K <= quad) COS_CONV_FWD(8, 4);
-  else if (w8)                                COS_CONV_FWD(8, 2);
-  else                                        COS_CONV_FWD(4, 2);
-#undef COS_CONV_FWD
+  bool w8 = use_w8(M, N);
+  bool q = quad && K >= 4 * BK && K <= quad;
+  // The narrow tiles follow the sweep in
+  // profiles/alexnet_1gpu_conv_tiles.md: 32x48 wave tiles at depth 2 for
+  // 96 columns (the depth-4 ring lost at K = 448 and 1152), 256-row
+  // blocks for 64 and 48 columns once M is large enough to fill the chip
+  // with them.  Small M was not swept; it keeps 128 rows and, for 64 and
+  // 48 columns, the fixed tile's depth rule (the COS_CONVQ gate).
+  bool big_m = M >= 8192;
+  int id;
+  switch (conv_bn(N)) {
+    case 96: id = w8 ? 4 : 3; break;
+    case 64: id = big_m ? 8 : w8 ? (q ? 7 : 6) : 5; break;
+    case 48: id = big_m ? 11 : q ? 10 : 9; break;
+    default: id = w8 ? (q ? 0 : 1) : 2; break;
+  }
+  return kConvCfgs[id];
+}
+
+// groups > 1 runs a grouped convolution in one launch; see the kernel
+// for the three strides.  cfg >= 0 forces an instantiation (the sweep).
+// vec: 0 element-wise epilogue, 1 the 16-byte one where the operands
+// allow it, -1 automatic (conv_vec).
+void gemm_conv_fwd(const void* X, const void* B, void* C,
+                   const float* bias, const void* zpage, int M, int N,
+                   int K, int ldb, int ldc, bool relu, bool accum,
+                   const int* geom, int groups, int gs_c, int gs_b,
+                   int gs_n, int cfg, int vec, hipStream_t stream) {
+  CGeom gm = make_geom(geom);
+  if (K % BK != 0 || K < 2 * BK)
+    throw std::runtime_error("gemm_conv_fwd: K must be whole 32-wide tiles, "
+                             "at least two");
+  if (cfg >= kNumConvCfgs)
+    throw std::runtime_error("gemm_conv_fwd: no such configuration");
+  ConvCfg p = cfg >= 0 ? kConvCfgs[cfg] : conv_fwd_plan(M, N, K);
+  int mblocks = (M + p.bm - 1) / p.bm, nblocks = (N + p.bn - 1) / p.bn;
+  dim3 grid(mblocks * nblocks, max(1, groups));
+  // the 16-byte epilogue needs whole, aligned 8-channel runs
+  bool vec_ok = ((N | ldc | (groups > 1 ? gs_n : 0)) % 8 == 0) &&
+                (((uintptr_t)C | (uintptr_t)bias) % 16 == 0);
+  int use_vec = vec_ok && (vec < 0 ? conv_vec(p.id) : vec != 0);
+  switch (p.id) {
+#define CFG_(ID, TBM, TBN, WM, WN, DEPTH)                                   \
+    case ID:                                                                \
+      gemm_conv_fwd_kernel<TileCfg<TBM, TBN, WM, WN>, DEPTH>                \
+          <<<grid, WM * WN * 64, 0, stream>>>(                              \
+              (const bf16*)X, (const bf16*)B, (bf16*)C, bias,               \
+              (const bf16*)zpage, M, N, K, ldb, ldc, relu ? 1 : 0,          \
+              accum ? 1 : 0, gm, gs_c, gs_b, gs_n, use_vec);                \
+      break;
+    COS_CONV_CFGS(CFG_)
+#undef CFG_
+  }
 }
 
 void gemm_conv_fwd_sc(const void* X, const void* B, void* C,

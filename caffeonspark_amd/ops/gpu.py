@@ -31,8 +31,8 @@ def _pad32(k: int) -> int:
 def _kpad_dma(k: int) -> int:
     """K extent of a GEMM run by the DMA-staged pipelined loop
     (gemm_conv_fwd, gemm_conv_fwd_sc): whole 32-wide tiles, and at least
-    two of them — with a single tile the loop's counted wait passes before
-    the tile's DMA has landed (gemm.hip, above ADirect).  The staging
+    two of them — the loop's prologue and peeled tail assume as many tiles
+    as it prefetches (gemm.hip, above ADirect).  The staging
     zero-fills k beyond the real extent and the B operand's pad columns
     are zero, so the padding adds only zeros."""
     return max(64, _pad32(k))
@@ -349,9 +349,10 @@ def conv2d_forward(x, w, b, stride, pad, dilation, groups, ctx=None,
         shadow = w if (w.dtype == torch.bfloat16 and
                        getattr(w, "_cos_stable", False)) \
             else getattr(w, "_cos_bf16", None)
-        # implicit-dx eligibility: stride-1 G==1 convs compute the data
-        # gradient as ONE implicit GEMM over dy with the flipped-weight
-        # layout wrF[c][(RS-1-rs)*Kout + k] (no dcol, no col2im)
+        # implicit-dx eligibility: stride-1 convs compute the data
+        # gradient as ONE implicit GEMM launch (all groups) over dy with
+        # the flipped-weight layout, per group wrF[c][(RS-1-rs)*Kg + k]
+        # (no dcol, no col2im)
         k2 = R * S * Kg
         dx_imp = implicit and _dx_imp_ok(N, H, W, R, S, sh, sw, ph, pw,
                                          dil, Kg)
@@ -432,14 +433,12 @@ def conv2d_forward(x, w, b, stride, pad, dilation, groups, ctx=None,
         col = None
     elif implicit:
         col = None
-        for g in range(G):
-            geom = [H, W, C, P, Q, sh, sw, ph, pw, dil, S, g * Cg, Cg,
-                    Kcol]
-            _ext.gemm_conv_fwd(
-                xl, wrb[g * Kg:], y2[:, g * Kg:],
-                bias_f[g * Kg:(g + 1) * Kg] if bias_f is not None
-                else None, _zpage(x.device), NPQ, Kg, Kpad, Kpad,
-                ldc_out, relu, False, geom)
+        # one launch for all groups: group g reads channels from g*Cg,
+        # wrb rows from g*Kg, and writes y2's columns from g*Kg
+        geom = [H, W, C, P, Q, sh, sw, ph, pw, dil, S, 0, Cg, Kcol]
+        _ext.gemm_conv_fwd(xl, wrb, y2, bias_f, _zpage(x.device), NPQ, Kg,
+                           Kpad, Kpad, ldc_out, relu, False, geom, G, Cg,
+                           Kg, Kg)
     elif implicit_sc:
         col = None
         # CGeom field reuse for the _sc kernels: S slot carries C,
@@ -651,17 +650,14 @@ def _conv_dx(dyl, dyg, ld_dy, shape, wr, wrT, wrF, dx, dx_acc=False):
     if wrF is not None and wrF.shape == (G * cgp, _kpad_dma(k2)) \
             and N * H * W < (1 << 20):
         # implicit dx: the data gradient IS a stride-1 convolution of
-        # dy with the flipped weights — one GEMM per group writes
+        # dy with the flipped weights — one grouped GEMM launch writes
         # dx's NHWC alias directly (no dcol buffer, no col2im pass)
         dx2 = dx.permute(0, 2, 3, 1).reshape(N * H * W, C)
-        for g in range(G):
-            geom = [P, Q, ld_dy, H, W, 1, 1,
-                    dil * (R - 1) - ph, dil * (S - 1) - pw, dil, S,
-                    g * Kg, Kg, k2]
-            _ext.gemm_conv_fwd(dyl, wrF[g * cgp:], dx2[:, g * Cg:],
-                               None, _zpage(dyl.device), N * H * W,
-                               Cg, _kpad_dma(k2), _kpad_dma(k2), C, False,
-                               dx_acc, geom)
+        geom = [P, Q, ld_dy, H, W, 1, 1,
+                dil * (R - 1) - ph, dil * (S - 1) - pw, dil, S, 0, Kg, k2]
+        _ext.gemm_conv_fwd(dyl, wrF, dx2, None, _zpage(dyl.device),
+                           N * H * W, Cg, _kpad_dma(k2), _kpad_dma(k2), C,
+                           False, dx_acc, geom, G, Kg, cgp, Cg)
         return
     dcol = torch.empty((NPQ, Kpad), dtype=torch.bfloat16,
                        device=dyl.device)

@@ -42,6 +42,9 @@ class LSTMLayer(Layer):
         self.stateful = bool(getattr(self.net, "recurrent_stateful", False))
         self._state = None
         self.step_route = None
+        # "persist" or "loop": which whole-sequence route the last
+        # forward / backward of the GPU sequence path took
+        self.seq_route = None
         self._wcast = {}
         n_in = len(bottom) - (2 if self.expose else 0)
         if n_in not in (2, 3):
@@ -196,7 +199,9 @@ class LSTMLayer(Layer):
         seq_fwd = ops.gpu_op("lstm_seq_forward") if x.is_cuda else None
         if seq_fwd is not None:
             # whole recurrence driven from C++ (3 kernel launches/step)
-            y, seq_cache = seq_fwd(xg, w_hc, cont)
+            ctx = {}
+            y, seq_cache = seq_fwd(xg, w_hc, cont, ctx)
+            self.seq_route = ctx["route"]
             top[0].data = y
             self._cache = ("seq", x, cont, seq_cache)
             return 0.0
@@ -299,7 +304,10 @@ class LSTMLayer(Layer):
         H = self.h
         dy = top[0].diff
         seq_bwd = ops.gpu_op("lstm_seq_backward")
-        dxg, dw_hc = seq_bwd(dy.reshape(T, N, H), self.weight(2), seq_cache)
+        ctx = {}
+        dxg, dw_hc = seq_bwd(dy.reshape(T, N, H), self.weight(2), seq_cache,
+                             ctx)
+        self.seq_route = ctx["route"]
         dxg_flat = dxg.reshape(T * N, 4 * H)
         x_flat = x.reshape(T * N, -1)
         # shared tail: input GEMM grads == a linear layer's backward

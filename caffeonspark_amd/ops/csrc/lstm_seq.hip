@@ -109,7 +109,8 @@ static int nb_(int64_t total) {
 // xg:[T,N,4H] bf16 (x@Wxc+b, precomputed), w_hc:[4H,H] bf16, cont:[T,N]
 // bf16; outputs h:[T,N,H] bf16, c:[T,N,H] f32, act:[T,N,4H] f32,
 // h_in:[T,N,H] bf16 (gated prev hidden, kept for the weight-grad GEMM);
-// hg: scratch [N,4H] bf16.
+// hg: scratch [N,4H] fp32, the split-K atomic target of the per-step
+// recurrent GEMM.
 void lstm_seq_fwd(const void* xg, const void* w_hc, const void* cont,
                   void* h, float* c, float* act, void* h_in, float* hg,
                   int T, int N, int H, int n_alloc_whc,

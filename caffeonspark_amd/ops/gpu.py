@@ -1765,10 +1765,12 @@ def lstm_step(x, h_prev, c_prev, cont, w_xc, b_c, w_hc, xs=None,
     return h, c
 
 
-def lstm_seq_forward(xg, w_hc, cont):
+def lstm_seq_forward(xg, w_hc, cont, ctx=None):
     """Whole-sequence LSTM forward driven from C++ (3 launches/step).
     xg: [T,N,4H] pre-activation input gates (x @ W_xc + b [+ static]),
-    cont: [T,N].  Returns (h [T,N,H] bf16, cache)."""
+    cont: [T,N].  Returns (h [T,N,H] bf16, cache).  ctx, when given, gets
+    ctx["route"]: "persist" (csrc/lstm_persist.hip) or "loop"
+    (csrc/lstm_seq.hip), whichever ran."""
     T, N, H4 = xg.shape
     H = H4 // 4
     dev_ = xg.device
@@ -1795,9 +1797,13 @@ def lstm_seq_forward(xg, w_hc, cont):
                                    bar)
         if rc == 0:
             _persist_track(bar)
+            if ctx is not None:
+                ctx["route"] = "persist"
             return h, (cont_b, h, c, act, h_in, T, N, H)
     _ext.lstm_seq_fwd(xg, whc[:H4], cont_b, h, c, act, h_in, hg,
                       T, N, H, whc.shape[0])
+    if ctx is not None:
+        ctx["route"] = "loop"
     return h, (cont_b, h, c, act, h_in, T, N, H)
 
 
@@ -1849,8 +1855,9 @@ def _lstm_persist_ok(N):
     return True
 
 
-def lstm_seq_backward(dy, w_hc, cache):
-    """Returns (dxg [T,N,4H] bf16, dw_hc fp32)."""
+def lstm_seq_backward(dy, w_hc, cache, ctx=None):
+    """Returns (dxg [T,N,4H] bf16, dw_hc fp32).  ctx["route"] as in
+    lstm_seq_forward."""
     cont_b, h, c, act, h_in, T, N, H = cache
     H4 = 4 * H
     dev_ = dy.device
@@ -1876,6 +1883,8 @@ def lstm_seq_backward(dy, w_hc, cache):
     if not done:
         _ext.lstm_seq_bwd(dy, whcT, cont_b, h, c, act, dxg, dh_rec, dh_f,
                           dc_a, dc_b, T, N, H, _pad128(H4))
+    if ctx is not None:
+        ctx["route"] = "persist" if done else "loop"
     # dw_hc = dgates_all^T @ h_in_all — fused trans/trans GEMM (u32
     # k-pair staging), no operand transposes
     dxg_flat = dxg.reshape(T * N, H4)

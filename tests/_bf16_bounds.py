@@ -73,6 +73,17 @@ Per op (n = local_size, m = rows = N*H*W):
             saturation).  Products propagate sum_k tol_k*prod_{j!=k}(|f_j|
             + tol_j).  c and act are fp32, h and dgates bf16 (+u*T).
  SGD        fp32 FMA chain, checked at rtol 1e-5 / atol 1e-6.
+
+The whole-sequence LSTM routes are bounded in _lstm_seq_cases.py by the same
+rules, one step at a time from the state the route itself emitted:
+
+ LSTM seq   forward pre = xg + h_in @ W^T: (H+4)e(|xg| + |h_in| @ |W|^T),
+ forward    then the LSTM-unit gate, c and h bounds; h_in[t] ==
+            bf16(h[t-1] cont[t]) bit-exact.
+ LSTM seq   dh_rec = cont (dxg[t+1] @ W): (4H+4)e(|dxg| @ |W|), plus u on
+ backward   the loop route, which stores it as bf16; dc carried in float64
+            with cont*gf*(tol + 4e*mag); dxg as the LSTM-unit dgates; dwhc
+            (TN+4)e(|dxg|^T @ |h_in|).
 """
 
 import torch

@@ -218,6 +218,62 @@ void bias_act_cast(const float* in, const float* bias, void* out,
       in, bias, (u16*)out, rows, cols, relu ? 1 : 0);
 }
 
+// bias_act_cast's successor for gemm_fc's slab split-K: out[m][n] =
+// bf16(act(sum_s slabs[s][m][n] + bias[n])), the slabs added in ascending
+// s — a fixed order, so the same bits on every run.  N % 8 == 0 takes the
+// 16-byte path (two float4 per slab in, eight bf16 out); else scalar.
+__global__ void fc_slab_finalize_kernel(const float* __restrict__ slabs,
+                                        int sk, const float* __restrict__ bias,
+                                        u16* __restrict__ out, int M, int N,
+                                        int ldo, int relu, int vec) {
+  int64_t slab = (int64_t)M * N;
+  int64_t start = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t step = (int64_t)gridDim.x * blockDim.x;
+  if (vec) {
+    int n8 = N / 8;
+    for (int64_t i = start; i < (int64_t)M * n8; i += step) {
+      int row = (int)(i / n8), col = (int)(i - (int64_t)row * n8) * 8;
+      const float* p = slabs + (int64_t)row * N + col;
+      float v[8] = {};
+      for (int s = 0; s < sk; ++s, p += slab) {
+        f32x4 lo = *reinterpret_cast<const f32x4*>(p);
+        f32x4 hi = *reinterpret_cast<const f32x4*>(p + 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { v[j] += lo[j]; v[4 + j] += hi[j]; }
+      }
+      u16x8 o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float f = v[j] + (bias != nullptr ? bias[col + j] : 0.f);
+        if (relu && f < 0.f) f = 0.f;
+        bf16 b = f2bf(f);
+        o[j] = *reinterpret_cast<u16*>(&b);
+      }
+      *reinterpret_cast<u16x8*>(out + (int64_t)row * ldo + col) = o;
+    }
+  } else {
+    for (int64_t i = start; i < slab; i += step) {
+      int row = (int)(i / N), col = (int)(i - (int64_t)row * N);
+      float v = 0.f;
+      for (int s = 0; s < sk; ++s) v += slabs[s * slab + i];
+      if (bias != nullptr) v += bias[col];
+      if (relu && v < 0.f) v = 0.f;
+      stbf(out + (int64_t)row * ldo + col, v);
+    }
+  }
+}
+
+void fc_slab_finalize(const float* slabs, int sk, const float* bias,
+                      void* out, int M, int N, int ldo, bool relu,
+                      hipStream_t stream) {
+  bool vec = N % 8 == 0 && ldo % 8 == 0 &&
+             (((uintptr_t)slabs | (uintptr_t)out) % 16 == 0);
+  int64_t work = vec ? (int64_t)M * (N / 8) : (int64_t)M * N;
+  int blocks = (int)hmin<int64_t>(2048, (work + 255) / 256);
+  fc_slab_finalize_kernel<<<blocks, 256, 0, stream>>>(
+      slabs, sk, bias, (u16*)out, M, N, ldo, relu ? 1 : 0, vec ? 1 : 0);
+}
+
 // ------------------------------------------------------------ transpose
 // Tiled 2D bf16 transpose [R][C] -> [C][R]: 64x64 tiles staged through
 // LDS (row pad 66 u16 -> conflict-free transposed reads), coalesced

@@ -16,6 +16,15 @@ void gemm_bf16(const void* A, const void* B, void* C, const float* bias,
                bool trans_a, bool trans_b, int store_mode, int splitk,
                bool relu, float alpha, int m_alloc, int n_alloc,
                hipStream_t stream);
+struct FcPlan { int route, bm, bn, depth, sk; };
+FcPlan fc_gemm_plan(int M, int N, int K, int kind, bool aligned);
+int gemm_fc(const void* A, const void* B, void* C, float* slabs,
+            const float* bias, const void* zpage, int M, int N, int K,
+            int lda, int ldb, int ldc, int kind, int sk, bool relu,
+            hipStream_t stream);
+void fc_slab_finalize(const float* slabs, int sk, const float* bias,
+                      void* out, int M, int N, int ldo, bool relu,
+                      hipStream_t stream);
 void gemm_f32(const float* A, const float* B, float* C, const float* bias,
               int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc,
               bool trans_a, bool trans_b, int splitk, bool relu,
@@ -227,6 +236,85 @@ void py_gemm(Tensor A, Tensor B, Tensor C, c10::optional<Tensor> bias,
       A.data_ptr(), B.data_ptr(), C.data_ptr(), bptr, (int)M, (int)N, (int)K, (int)lda, (int)ldb, (int)ldc,
       trans_a, trans_b, (int)store_mode, (int)splitk, relu, (float)alpha,
       (int)m_alloc, (int)n_alloc, cur_stream());
+}
+
+// (route, BM, BN, ring depth, sk) of the InnerProduct GEMM [M, N, K];
+// kind 0 forward, 1 data gradient; route 1 = gemm_fc, 0 = legacy
+std::vector<int64_t> py_fc_gemm_plan(int64_t M, int64_t N, int64_t K,
+                                     int64_t kind, bool aligned) {
+  cosamd::FcPlan p = cosamd::fc_gemm_plan((int)M, (int)N, (int)K, (int)kind,
+                                          aligned);
+  return {p.route, p.bm, p.bn, p.depth, p.sk};
+}
+
+// C = A @ op(B) by the weight-streaming kernel; A, B and C may be views
+// (lda / ldb / ldc in elements), so their extents are checked against
+// their storage here.  Returns the number of slabs written (1: C holds
+// the result; more: finish with fc_slab_finalize).
+int64_t py_gemm_fc(Tensor A, Tensor B, Tensor C, c10::optional<Tensor> slabs,
+                   c10::optional<Tensor> bias, Tensor zpage, int64_t M,
+                   int64_t N, int64_t K, int64_t lda, int64_t ldb,
+                   int64_t ldc, int64_t kind, int64_t sk, bool relu) {
+  CHECK_CUDA(A); CHECK_CUDA(B); CHECK_CUDA(C); CHECK_CUDA(zpage);
+  CHECK_BF16(A); CHECK_BF16(B); CHECK_BF16(C); CHECK_BF16(zpage);
+  TORCH_CHECK(zpage.numel() >= 8, "zpage must hold 16 zero bytes");
+  TORCH_CHECK(M > 0 && N > 0 && K > 0 && sk <= 65535, "gemm_fc: bad size");
+  auto span = [](const Tensor& t) {
+    return (int64_t)(t.storage().nbytes() / t.element_size()) -
+           t.storage_offset();
+  };
+  int64_t br = kind == 1 ? K : N, bc = kind == 1 ? N : K;
+  TORCH_CHECK(lda >= K && ldb >= bc && ldc >= N,
+              "gemm_fc: leading dimension smaller than the row");
+  TORCH_CHECK((M - 1) * lda + K <= span(A), "gemm_fc: A too small");
+  TORCH_CHECK((br - 1) * ldb + bc <= span(B), "gemm_fc: B too small");
+  TORCH_CHECK((M - 1) * ldc + N <= span(C), "gemm_fc: C too small");
+  float* sp = nullptr;
+  if (slabs.has_value()) {
+    const Tensor& s = slabs.value();
+    CHECK_CUDA(s); CHECK_F32(s);
+    int64_t want = sk > 0 ? sk : cosamd::fc_gemm_plan(
+        (int)M, (int)N, (int)K, (int)kind, true).sk;
+    // split_k() of gemm.hip: whole 32-wide tiles per split
+    int64_t ksplit = ((K + want - 1) / want + 31) / 32 * 32;
+    int64_t need = (K + ksplit - 1) / ksplit;
+    TORCH_CHECK(s.is_contiguous() && s.numel() >= need * M * N,
+                "gemm_fc: slabs must hold one [M, N] slab per split");
+    sp = s.data_ptr<float>();
+  }
+  const float* bptr = nullptr;
+  if (bias.has_value()) {
+    const Tensor& b = bias.value();
+    CHECK_CUDA(b); CHECK_F32(b);
+    TORCH_CHECK(b.is_contiguous() && b.numel() >= N,
+                "gemm_fc: bias must hold N contiguous floats");
+    bptr = b.data_ptr<float>();
+  }
+  return cosamd::gemm_fc(A.data_ptr(), B.data_ptr(), C.data_ptr(), sp, bptr,
+                         zpage.data_ptr(), (int)M, (int)N, (int)K, (int)lda,
+                         (int)ldb, (int)ldc, (int)kind, (int)sk, relu,
+                         cur_stream());
+}
+
+void py_fc_slab_finalize(Tensor slabs, int64_t sk, c10::optional<Tensor> bias,
+                         Tensor out, int64_t M, int64_t N, int64_t ldo,
+                         bool relu) {
+  CHECK_CUDA(slabs); CHECK_F32(slabs); CHECK_CUDA(out); CHECK_BF16(out);
+  TORCH_CHECK(sk >= 1 && slabs.is_contiguous() &&
+              slabs.numel() >= sk * M * N, "fc_slab_finalize: slabs too small");
+  TORCH_CHECK(ldo >= N && (M - 1) * ldo + N <=
+              (int64_t)(out.storage().nbytes() / 2) - out.storage_offset(),
+              "fc_slab_finalize: out too small");
+  const float* bptr = nullptr;
+  if (bias.has_value()) {
+    CHECK_F32(bias.value());
+    TORCH_CHECK(bias.value().is_contiguous() && bias.value().numel() >= N,
+                "fc_slab_finalize: bias must hold N contiguous floats");
+    bptr = bias.value().data_ptr<float>();
+  }
+  cosamd::fc_slab_finalize(slabs.data_ptr<float>(), (int)sk, bptr,
+                           out.data_ptr(), (int)M, (int)N, (int)ldo, relu,
+                           cur_stream());
 }
 
 // elements addressable from t's first element to the end of its storage
@@ -966,6 +1054,10 @@ void py_softmax_loss_bwd(Tensor prob, Tensor label, Tensor dx, double scale,
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm", &py_gemm);
+  m.def("fc_gemm_plan", &py_fc_gemm_plan, py::arg("M"), py::arg("N"),
+        py::arg("K"), py::arg("kind"), py::arg("aligned") = true);
+  m.def("gemm_fc", &py_gemm_fc);
+  m.def("fc_slab_finalize", &py_fc_slab_finalize);
   m.def("gemm_f32", &py_gemm_f32);
   m.def("im2col_f32", &py_im2col_f32);
   m.def("col2im_f32", &py_col2im_f32);

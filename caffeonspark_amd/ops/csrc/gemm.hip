@@ -21,6 +21,7 @@
 //   epilogue_bf16    bias + ReLU + alpha, bf16 store or RMW accumulate
 //   epilogue_bf16_vec  the same through LDS with 16-byte accesses (conv)
 //   epilogue_f32     fp32 plain store or atomic add (split-K)
+//   epilogue_f32_vec   the plain store through LDS with 16-byte accesses
 //
 // Kernels, their staging policies, and who launches them:
 //   gemm_kernel<TA, TB, STORE_MODE, WAVES>       gemm_bf16[_batched]
@@ -64,6 +65,14 @@
 //     ds_read_b64_tr_b16.  Taken when db == nullptr and every 16-byte
 //     source chunk is aligned and whole (M, lda, C, c0, Cg, Kcol % 8 == 0,
 //     A and X 16-byte aligned); COS_DW_TR=0 forces the fallback.
+//   gemm_fc_kernel<TBM, TRB, DEPTH>              gemm_fc
+//     InnerProduct forward (TRB false) and data gradient (TRB true) for
+//     M <= 256: a 256x128 (M <= 128: 128x128) tile that covers all of M,
+//     8 waves, both operands DMA-staged into a depth-4 ring with
+//     gemm_conv_dw_tr_kernel's loop, W read as it lies (transposing LDS
+//     reads for dx), zero-page edges, split-K into fp32 slabs
+//     (epilogue_f32_vec) that fc_slab_finalize sums.  fc_gemm_plan picks
+//     route and split; COS_FC_STREAM=0 keeps gemm_kernel.  See its section.
 // w8 (use_w8): 8-wave blocks when M or N <= 256, forced by COS_GEMM_W8.
 //
 // Replaces the reference's cuBLAS calls inside conv/ip layers (SURVEY.md
@@ -314,6 +323,50 @@ __device__ __forceinline__ void epilogue_f32(
           atomicAdd(C + (int64_t)row * ldc + col, v);
       }
     }
+  }
+}
+
+// 16-byte form of epilogue_f32's plain store (no bias), for gemm_fc_kernel's
+// slabs (tried on gemm_wide_tt_kernel's dW store too: no gain at the three
+// AlexNet FC shapes, profiles/alexnet_1gpu_fc_stream.md): a wave
+// transposes its accumulators, one 16-row band at a time, through a
+// private LDS slab (16 rows of NCOLS + 4 floats, as epilogue_bf16_vec) so
+// that a lane holds 4 consecutive columns of one row and a store
+// instruction covers whole 256-byte (NCOLS = 64) row segments instead of
+// 64-byte ones.  The same floats reach the same addresses.  The caller
+// guarantees N, ldc and col0 are multiples of 4, C is 16-byte aligned and
+// nothing else uses `slab` any more.  row0 / col0: the wave tile's origin.
+template <int NCOLS>
+constexpr int f32_slab_floats() { return 16 * (NCOLS + 4); }
+
+template <int MF, int NF, int NCOLS>
+__device__ __forceinline__ void epilogue_f32_vec(
+    const f32x4 (&acc)[MF][NF], float* slab, float* C, int M, int N, int ldc,
+    int row0, int col0, int lane, float alpha) {
+  constexpr int LD = NCOLS + 4;
+  constexpr int GPR = NCOLS / 4;             // 4-column groups per row
+  constexpr int TASKS = 16 * GPR;            // (row, group) pairs per band
+  static_assert(TASKS % 64 == 0, "whole wave-instructions per band");
+  int wr = (lane >> 4) << 2, wc = lane & 15;
+#pragma unroll
+  for (int fm = 0; fm < MF; ++fm) {
+#pragma unroll
+    for (int fn = 0; fn < NF; ++fn)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        slab[(wr + r) * LD + fn * 16 + wc] = acc[fm][fn][r] * alpha;
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int t0 = 0; t0 < TASKS; t0 += 64) {
+      int t = t0 + lane;
+      int row = t / GPR, cg = t - row * GPR;
+      int grow = row0 + fm * 16 + row;
+      int col = col0 + cg * 4;
+      if (grow < M && col < N)
+        *reinterpret_cast<f32x4*>(C + (int64_t)grow * ldc + col) =
+            *reinterpret_cast<const f32x4*>(slab + row * LD + cg * 4);
+    }
+    __builtin_amdgcn_wave_barrier();
   }
 }
 
@@ -1616,6 +1669,305 @@ void gemm_bf16(const void* A_, const void* B_, void* C, const float* bias,
   gemm_bf16_batched(A_, B_, C, bias, M, N, K, lda, ldb, ldc, trans_a,
                     trans_b, store_mode, splitk, relu, alpha, m_alloc,
                     n_alloc, 1, 0, 0, 0, stream);
+}
+
+// ------------------------------------- weight-streaming InnerProduct GEMM
+// C[M,N] = A[M,K] @ B' for skinny activations (M <= 256): the forward pass
+// (B = W stored [N][K], TRB false) and the data gradient (B = W stored
+// [K][N], N contiguous, TRB true) of an InnerProduct layer.  These GEMMs
+// are bound by the bytes of W, so:
+//   - one block covers all of M (TBM = 256, or 128 when M <= 128): every
+//     weight byte is fetched by exactly one block, once;
+//   - both operands are staged by direct-to-LDS DMA into a DEPTH-stage ring
+//     (DEPTH - 1 tiles, 72 KB at depth 4, in flight per CU), with the
+//     counted-vmcnt loop of gemm_conv_dw_tr_kernel: every DMA always
+//     issues — rows beyond M or N, k beyond the split's end and the tiles
+//     prefetched past it fetch the zero page — so the count is exact for
+//     any tile count >= 1 and edges need no padded copies.  K % 8 == 0
+//     keeps every 16-byte chunk wholly inside or outside its operand;
+//   - TRB stages W as it lies, [32 k][128 col] in gemm_conv_dw_tr_kernel's
+//     swizzled image, and reads fragments with ds_read_b64_tr_b16: no
+//     transposed copy of W exists;
+//   - split-K writes slabs, not atomics: split s stores its fp32 partial
+//     tile with plain 16-byte stores into slab s of a [sk][M][N] workspace,
+//     every element of every slab; fc_slab_finalize (elementwise.hip) sums
+//     them in ascending s, so the result is the same bits on every run.
+//     A single split stores bf16 directly with bias and ReLU fused.
+// LDS image of a stage: A, [TBM][32] canonical (swz_chunk), then B, 8 KB:
+// canonical [128][32] or the transposed [32][128] image.  All LDS reads are
+// inline assembly for the reason given at ds_read_tr16.
+
+constexpr int FC_BN = 128;
+constexpr int FC_DEPTH = 4;
+
+struct FcPlan { int route, bm, bn, depth, sk; };
+
+__device__ __forceinline__ bf16x8 ds_read_b128_asm(unsigned addr) {
+  bf16x8 v;
+  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
+  return v;
+}
+
+template <int TBM, bool TRB, int DEPTH>
+__global__ __launch_bounds__(512, 1) void gemm_fc_kernel(
+    const bf16* __restrict__ A, const bf16* __restrict__ B,
+    const bf16* __restrict__ zpage, bf16* __restrict__ Cb,
+    float* __restrict__ Cs, const float* __restrict__ bias, int M, int N,
+    int K, int lda, int ldb, int ldc, int ksplit, int relu, int vec) {
+  constexpr int WM = TBM / 64, WN = 8 / WM;      // 4x2 or 2x4 waves
+  using Cfg = TileCfg<TBM, FC_BN, WM, WN>;       // 64 x (64 | 32) per wave
+  constexpr int MF = Cfg::MF, NF = Cfg::NF, NCOLS = Cfg::NCOLS;
+  constexpr int A_BYTES = TBM * BK * 2, B_BYTES = FC_BN * BK * 2;
+  constexpr int STAGE = A_BYTES + B_BYTES;
+  constexpr int A_CPW = Cfg::A_CPW;              // 1 KB A chunks per wave
+  static_assert(MF == 4 && Cfg::B_CHUNKS == 8, "one B chunk per wave");
+  static_assert(DEPTH * STAGE >= vec_slab_floats<Cfg>() * 4 &&
+                DEPTH * STAGE >= 8 * f32_slab_floats<NCOLS>() * 4,
+                "the epilogue slabs fit in the ring");
+  __shared__ __attribute__((aligned(16))) unsigned char smem[DEPTH * STAGE];
+
+  int tile_n = blockIdx.x * FC_BN;
+  int k_begin = blockIdx.y * ksplit;
+  int k_end = min(K, k_begin + ksplit);
+
+  int tid = threadIdx.x;
+  int wave = tid >> 6, lane = tid & 63;
+  int wm = wave / WN, wn = wave % WN;
+
+  // ---- staging, fixed per lane but for the K tile.  A chunk c holds rows
+  // 16c..16c+15; lane l fills chunk position (row l/4, l%4) and so fetches
+  // the source chunk the swizzle maps there (stage_direct_fast).
+  const unsigned short* as = reinterpret_cast<const unsigned short*>(A);
+  const unsigned short* bs = reinterpret_cast<const unsigned short*>(B);
+  int64_t a_off[A_CPW];
+  int a_kk[A_CPW];
+  bool a_ok[A_CPW];
+#pragma unroll
+  for (int it = 0; it < A_CPW; ++it) {
+    int row = (wave * A_CPW + it) * 16 + (lane >> 2);
+    a_kk[it] = swz_chunk(row, lane & 3) << 3;
+    a_ok[it] = row < M;
+    a_off[it] = (int64_t)row * lda + a_kk[it];
+  }
+  int64_t b_off;
+  int b_kk;
+  bool b_ok;
+  if (TRB) {
+    // wave w fills k-rows 4w..4w+3 of the [32][128] image
+    int srow = wave * 4 + (lane >> 4);
+    int sch = (dw_tr_off(srow, lane & 15) >> 4) & 15;
+    int col = tile_n + sch * 8;                  // N % 8 == 0: whole octets
+    b_kk = srow;
+    b_ok = col < N;
+    b_off = (int64_t)srow * ldb + col;
+  } else {
+    int row = wave * 16 + (lane >> 2);
+    b_kk = swz_chunk(row, lane & 3) << 3;
+    b_ok = tile_n + row < N;
+    b_off = (int64_t)(tile_n + row) * ldb + b_kk;
+  }
+  typedef const __attribute__((address_space(1))) unsigned int* gptr;
+  typedef __attribute__((address_space(3))) unsigned int* lptr;
+  // branch-free select, as in gemm_conv_dw_tr_kernel: one DMA per chunk
+  // with EXEC all ones, whatever the guards say
+  auto keep_v = [](int64_t v) {
+    asm volatile("" : "+v"(v));
+    return v;
+  };
+  auto stage = [&](int slot, int k0) {
+    unsigned char* base = smem + slot * STAGE;
+#pragma unroll
+    for (int it = 0; it < A_CPW; ++it) {
+      bool ok = a_ok[it] & (k0 + a_kk[it] < k_end);
+      int64_t off = keep_v(a_off[it] + k0);
+      const void* src = ok ? (const void*)(as + off) : (const void*)zpage;
+      __builtin_amdgcn_global_load_lds(
+          (gptr)src, (lptr)(base + (wave * A_CPW + it) * 1024), 16, 0, 0);
+    }
+    bool ok = b_ok & (k0 + b_kk < k_end);
+    int64_t off = keep_v(b_off + (TRB ? (int64_t)k0 * ldb : (int64_t)k0));
+    const void* src = ok ? (const void*)(bs + off) : (const void*)zpage;
+    __builtin_amdgcn_global_load_lds(
+        (gptr)src, (lptr)(base + A_BYTES + wave * 1024), 16, 0, 0);
+  };
+
+  // ---- fragment read addresses inside a stage (fixed per lane)
+  int lrow = lane & 15, lchunk = lane >> 4;
+  int a_addr[MF], b_addr[NF][2];
+#pragma unroll
+  for (int f = 0; f < MF; ++f) {
+    int ra = wm * 64 + f * 16 + lrow;
+    a_addr[f] = ra * 64 + (swz_chunk(ra, lchunk) << 4);
+  }
+  if (TRB) {
+    // group g = lane>>4 reads k-rows 8g+4h+q; lane 4q+p of the group
+    // supplies columns 4p..4p+3 of fragment f's 16 columns
+    int fq = (lane >> 2) & 3, fp = lane & 3;
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        b_addr[f][h] = A_BYTES +
+            dw_tr_off(8 * lchunk + 4 * h + fq,
+                      (wn * NCOLS + f * 16) / 8 + (fp >> 1)) + 8 * (fp & 1);
+  } else {
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+      int rb = wn * NCOLS + f * 16 + lrow;
+      b_addr[f][0] = b_addr[f][1] =
+          A_BYTES + rb * 64 + (swz_chunk(rb, lchunk) << 4);
+    }
+  }
+  unsigned lds0 = (unsigned)(uintptr_t)(
+      (__attribute__((address_space(3))) unsigned char*)smem);
+
+  f32x4 acc[MF][NF] = {};
+
+  constexpr int PF = DEPTH - 1;              // tiles in flight ahead
+  constexpr int VMCNT = (A_CPW + 1) * (PF - 1);
+  int tiles = (k_end - k_begin + BK - 1) / BK;
+#pragma unroll
+  for (int p = 0; p < PF; ++p) stage(p, k_begin + p * BK);
+  int cur = 0;                               // ring slot of tile i
+  for (int i = 0; i < tiles; ++i) {
+    wait_vmcnt<VMCNT>();                     // this wave's part of tile i
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();            // everyone's; tile i-1 is read
+    int nxt = cur == 0 ? DEPTH - 1 : cur - 1;     // (i + PF) % DEPTH
+    stage(nxt, k_begin + (i + PF) * BK);
+    unsigned img = lds0 + cur * STAGE;
+    bf16x8 afrag[MF], bfrag[NF];
+    if (TRB) {
+      bf16x4 br[NF][2];
+#pragma unroll
+      for (int f = 0; f < NF; ++f)
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+          br[f][h] = ds_read_tr16(img + b_addr[f][h]);
+#pragma unroll
+      for (int f = 0; f < MF; ++f) afrag[f] = ds_read_b128_asm(img + a_addr[f]);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int f = 0; f < NF; ++f) {
+        asm volatile("" : "+v"(br[f][0]), "+v"(br[f][1]));
+        bfrag[f] = __builtin_shufflevector(br[f][0], br[f][1], 0, 1, 2, 3, 4,
+                                           5, 6, 7);
+      }
+    } else {
+#pragma unroll
+      for (int f = 0; f < NF; ++f)
+        bfrag[f] = ds_read_b128_asm(img + b_addr[f][0]);
+#pragma unroll
+      for (int f = 0; f < MF; ++f) afrag[f] = ds_read_b128_asm(img + a_addr[f]);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int f = 0; f < NF; ++f) asm volatile("" : "+v"(bfrag[f]));
+    }
+    // the reads have landed: tie every fragment behind the wait so that
+    // no MFMA is scheduled above it
+#pragma unroll
+    for (int f = 0; f < MF; ++f) asm volatile("" : "+v"(afrag[f]));
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int fm = 0; fm < MF; ++fm)
+#pragma unroll
+      for (int fn = 0; fn < NF; ++fn)
+        acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            afrag[fm], bfrag[fn], acc[fm][fn], 0, 0, 0);
+    __builtin_amdgcn_s_setprio(0);
+    cur = cur + 1 == DEPTH ? 0 : cur + 1;
+  }
+  wait_vmcnt<0>();                           // the zero-page tail DMAs
+
+  float* lds_f = reinterpret_cast<float*>(smem);
+  if (Cs != nullptr) {
+    // split s: plain stores into slab s, every element of it
+    float* slab = Cs + (int64_t)blockIdx.y * M * N;
+    if (vec) {
+      __syncthreads();     // every wave's DMA has landed and its reads too
+      epilogue_f32_vec<MF, NF, NCOLS>(
+          acc, lds_f + wave * f32_slab_floats<NCOLS>(), slab, M, N, N,
+          wm * 64, tile_n + wn * NCOLS, lane, 1.f);
+    } else {
+      int crow0 = wm * 64 + (lchunk << 2), ccol0 = tile_n + wn * NCOLS + lrow;
+#pragma unroll
+      for (int fm = 0; fm < MF; ++fm)
+#pragma unroll
+        for (int fn = 0; fn < NF; ++fn)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            int row = crow0 + fm * 16 + r, col = ccol0 + fn * 16;
+            if (row < M && col < N)
+              slab[(int64_t)row * N + col] = acc[fm][fn][r];
+          }
+    }
+  } else if (vec) {
+    __syncthreads();
+    epilogue_bf16_vec<Cfg>(acc, lds_f, Cb, bias, M, N, ldc, 0, tile_n, wm, wn,
+                           wave, lane, relu, 0);
+  } else {
+    epilogue_bf16<MF, 64, NF, NCOLS>(acc, Cb, bias, M, N, ldc, 0, tile_n, wm,
+                                     wn, lane, relu, 1.f, std::false_type{});
+  }
+}
+
+// The plan for [M, N, K] of kind 0 (forward, W is [N][K]) or 1 (data
+// gradient, W is [K][N]): route 1 = gemm_fc_kernel, 0 = the caller's
+// legacy route.  `aligned`: A and B are 16-byte aligned with leading
+// dimensions that are multiples of 8 (the caller's to check; the launcher
+// checks again).  C may lie anyhow: only the 16-byte epilogue asks more.  COS_FC_STREAM=0 sends everything to the legacy route; it
+// is read per call because the tests flip it inside one process.
+// sk: about one block per CU in a single wave of blocks, every split at
+// least 256 of K, at most 16 slabs.
+FcPlan fc_gemm_plan(int M, int N, int K, int kind, bool aligned) {
+  const char* e = getenv("COS_FC_STREAM");
+  bool on = !(e && e[0] == '0');
+  FcPlan p{0, 0, FC_BN, FC_DEPTH, 1};
+  if (!on || !aligned || M < 1 || M > 256 || N < 1 || K < 8 || K % 8 != 0 ||
+      (kind == 1 && N % 8 != 0) || (kind != 0 && kind != 1))
+    return p;
+  p.route = 1;
+  p.bm = M <= 128 ? 128 : 256;
+  int ntiles = (N + FC_BN - 1) / FC_BN;
+  p.sk = hmax(1, hmin(hmin(K / 256, 256 / ntiles), 16));
+  return p;
+}
+
+// sk <= 0: the plan's.  sk == 1 stores bf16 into C (bias, ReLU fused);
+// sk > 1 fills `slabs` ([zblocks][M][N] fp32, at least sk of them) and
+// returns the number of slabs written (the K tiles may divide into fewer
+// than sk), for fc_slab_finalize to sum.
+int gemm_fc(const void* A, const void* B, void* C, float* slabs,
+            const float* bias, const void* zpage, int M, int N, int K,
+            int lda, int ldb, int ldc, int kind, int sk, bool relu,
+            hipStream_t stream) {
+  bool aligned = (((uintptr_t)A | (uintptr_t)B | (uintptr_t)zpage) % 16 ==
+                  0) && ((lda | ldb) % 8 == 0);
+  FcPlan p = fc_gemm_plan(M, N, K, kind, aligned);
+  if (!p.route || zpage == nullptr || lda < K || ldc < N ||
+      ldb < (kind == 1 ? N : K))
+    throw std::runtime_error("gemm_fc: shape or alignment outside the "
+                             "streaming kernel (see fc_gemm_plan)");
+  SplitK s = split_k(K, sk > 0 ? sk : p.sk);
+  if (s.zblocks > 1 && slabs == nullptr)
+    throw std::runtime_error("gemm_fc: split-K needs the slab workspace");
+  float* cs = s.zblocks > 1 ? slabs : nullptr;
+  int vec = cs != nullptr
+                ? (N % 4 == 0 && (uintptr_t)cs % 16 == 0)
+                : ((N | ldc) % 8 == 0 && (uintptr_t)C % 16 == 0 &&
+                   (bias == nullptr || (uintptr_t)bias % 16 == 0));
+  dim3 grid((N + FC_BN - 1) / FC_BN, s.zblocks);
+#define COS_FC_CASE(TBM, TRB)                                               \
+  gemm_fc_kernel<TBM, TRB, FC_DEPTH><<<grid, 512, 0, stream>>>(             \
+      (const bf16*)A, (const bf16*)B, (const bf16*)zpage, (bf16*)C, cs,     \
+      bias, M, N, K, lda, ldb, ldc, s.ksplit, relu ? 1 : 0, vec)
+  if (p.bm == 128) {
+    if (kind == 1) COS_FC_CASE(128, true); else COS_FC_CASE(128, false);
+  } else {
+    if (kind == 1) COS_FC_CASE(256, true); else COS_FC_CASE(256, false);
+  }
+#undef COS_FC_CASE
+  return s.zblocks;
 }
 
 }  // namespace cosamd

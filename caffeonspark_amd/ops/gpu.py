@@ -1057,19 +1057,64 @@ def deconv2d_backward(x, w, dy, stride, pad, dilation, groups,
 
 # ----------------------------------------------------------------- linear
 
+def _fc_aligned(*ts):
+    """The streaming FC kernel's operand gate: unit column stride, 16-byte
+    aligned bases, row strides that are multiples of 8 elements."""
+    return all(t.dim() == 2 and (t.stride(1) == 1 or t.shape[1] == 1)
+               and t.data_ptr() % 16 == 0 and t.stride(0) % 8 == 0
+               and t.stride(0) >= t.shape[1] for t in ts)
+
+
+def fc_gemm_plan(M, N, K, kind, aligned=True):
+    """(route, BM, BN, depth, sk) of an InnerProduct GEMM: kind "fwd"
+    (y[M,N] = x[M,K] W[N,K]^T) or "dx" (dx[M,N] = dy[M,K] W[K,N]); route
+    is "stream" (gemm_fc_kernel) or "legacy".  COS_FC_STREAM=0 gives
+    "legacy" everywhere; it is read on every call."""
+    r, bm, bn, depth, sk = _ext.fc_gemm_plan(
+        M, N, K, {"fwd": 0, "dx": 1}[kind], aligned)
+    return ("stream" if r else "legacy"), bm, bn, depth, sk
+
+
+def _fc_stream(a, wb, out, bias_f, kind, relu, sk, slabs=None):
+    """out[M,N] = a[M,K] @ op(wb) through gemm_fc: one launch, or with
+    sk > 1 the slab split-K and its finalize.  slabs: a [sk, M, N] fp32
+    workspace to use (every element is overwritten); None allocates."""
+    M, K = a.shape
+    N = out.shape[1]
+    if sk > 1 and slabs is None:
+        slabs = torch.empty((sk, M, N), dtype=torch.float32,
+                            device=a.device)
+    wrote = _ext.gemm_fc(a, wb, out, slabs if sk > 1 else None, bias_f,
+                         _zpage(a.device), M, N, K, a.stride(0),
+                         wb.stride(0), out.stride(0),
+                         {"fwd": 0, "dx": 1}[kind], sk, relu)
+    if wrote > 1:
+        _ext.fc_slab_finalize(slabs, wrote, bias_f, out, M, N,
+                              out.stride(0), relu)
+    return out
+
+
 def fc_forward(x, w, b, relu=False):
     _check_bf16(x, "fc input")
     x = x.contiguous()
     M, K = x.shape
     Nout = w.shape[0]
+    w16 = _as_bf16(w)
+    route, _, _, _, sk = fc_gemm_plan(M, Nout, K, "fwd",
+                                      _fc_aligned(x, w16))
+    if route == "stream":
+        # weights streamed once as they lie: no padded copy, no zero fill
+        y = torch.empty((M, Nout), dtype=torch.bfloat16, device=x.device)
+        bias_f = b.float().contiguous() if b is not None else None
+        return _fc_stream(x, w16, y, bias_f, "fwd", relu, sk)
     if Nout % 128:
         wb = torch.zeros((_pad128(Nout), K), dtype=torch.bfloat16,
                          device=x.device)
-        wb[:Nout] = _as_bf16(w)
+        wb[:Nout] = w16
         na = wb.shape[0]
         wb = wb[:Nout]
     else:
-        wb = _as_bf16(w).contiguous()
+        wb = w16.contiguous()
         na = Nout
     y = torch.empty((M, Nout), dtype=torch.bfloat16, device=x.device)
     bias_f = b.float().contiguous() if b is not None else None
@@ -1093,7 +1138,8 @@ def fc_backward(x, w, dy, need_dx=True, bias=True, dw_out=None,
     _check_bf16(dy, "fc dy")
     x = x.contiguous()
     dy = dy.contiguous()
-    wb = _as_bf16(w).contiguous()
+    w16 = _as_bf16(w)
+    wb = w16.contiguous()
     M, K = x.shape
     Nout = wb.shape[0]
     dx = dw = db = None
@@ -1114,7 +1160,21 @@ def fc_backward(x, w, dy, need_dx=True, bias=True, dw_out=None,
                             zero_each_step=False)
         wb_p[:Nout] = wb
         wb = wb_p
+    dx_route, dx_sk = "legacy", 1
     if need_dx:
+        # (a transposed InnerProduct's w is a view: legacy, as before)
+        dx_route, _, _, _, dx_sk = fc_gemm_plan(
+            M, K, Np, "dx", _fc_aligned(dy, wb, w16))
+    if need_dx and dx_route == "stream":
+        # dx = dy @ w with w staged as it lies and transposed on the way
+        # out of LDS: no transposed copy.  The slabs are persistent
+        # scratch so that captured graphs keep their addresses; every
+        # element is overwritten, so they are never zeroed.
+        dx = torch.empty((M, K), dtype=torch.bfloat16, device=x.device)
+        slabs = _scratch_buf((dx_sk, M, K), torch.float32, x.device,
+                             zero_each_step=False) if dx_sk > 1 else None
+        _fc_stream(dy, wb, dx, None, "dx", False, dx_sk, slabs)
+    elif need_dx:
         # dx = dy @ w: transpose w once -> NT direct/direct fast staging.
         # With padded dy the K dim runs to Np (the pad columns multiply
         # wT's over-allocated junk rows by zero).

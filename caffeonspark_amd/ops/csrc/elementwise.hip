@@ -352,8 +352,15 @@ void transpose_bf16(const void* in, void* out, int64_t R, int64_t C,
       (const u16*)in, (u16*)out, (int)R, (int)C, tiles_c);
 }
 
-// one launch for ALL (lr_mult, decay_mult) segments of the flat arena:
-// blocks are striped across segments proportionally to their size
+// one launch for ALL (lr_mult, decay_mult) segments of the flat arena.
+// The arena is packed: a segment starts wherever the previous one ends.
+// A thread takes one quad (elements 4i .. 4i+3) per grid-stride iteration
+// and keeps a forward-only cursor s into the segment table.  A quad that
+// lies wholly inside segment s is updated with that segment's lr / wd (as
+// one 16-byte access per array in the SGD kernel); any other quad is
+// walked element by element, the cursor advancing with it, so every
+// element gets the parameters of the segment that owns it and only the
+// elements of a frozen (lr == 0) segment are skipped.
 // segment table cached in LDS (a per-quad global scan serializes on
 // dependent loads: measured 241us -> bandwidth-bound after this)
 #define COS_SGD_MAX_SEG 512
@@ -375,9 +382,9 @@ __global__ void sgd_update_multi_kernel(
        i < total4; i += (int64_t)gridDim.x * blockDim.x) {
     int64_t e0 = i * 4;
     while (s + 1 < nseg && e0 >= soff[s + 1]) ++s;
-    float lr = slr[s], wd = swd[s];
-    if (lr == 0.f) continue;
-    if (soff[s + 1] >= e0 + 4) {         // interior quad: vector path
+    if (soff[s] <= e0 && e0 + 4 <= soff[s + 1]) {   // interior quad
+      float lr = slr[s], wd = swd[s];
+      if (lr == 0.f) continue;
       f32x4 pv = *reinterpret_cast<f32x4*>(p + e0);
       f32x4 gv = *reinterpret_cast<const f32x4*>(g + e0);
       f32x4 vv = *reinterpret_cast<f32x4*>(v + e0);
@@ -400,9 +407,12 @@ __global__ void sgd_update_multi_kernel(
         }
         *reinterpret_cast<u16x4*>(sh + e0) = o;
       }
-    } else {
-      int64_t end = soff[s + 1];
+    } else {                             // holds a boundary or the tail
+      int64_t end = min(e0 + 4, soff[nseg]);
       for (int64_t k = e0; k < end; ++k) {
+        while (s + 1 < nseg && k >= soff[s + 1]) ++s;
+        float lr = slr[s], wd = swd[s];
+        if (lr == 0.f) continue;
         float gg = g[k] + wd * p[k];
         v[k] = mu * v[k] + lr * gg;
         p[k] -= v[k];
@@ -443,11 +453,11 @@ __global__ void nesterov_update_multi_kernel(
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
        i < total4; i += (int64_t)gridDim.x * blockDim.x) {
     int64_t e0 = i * 4;
-    while (s + 1 < nseg && e0 >= soff[s + 1]) ++s;
-    float lr = slr[s], wd = swd[s];
-    if (lr == 0.f) continue;
-    int64_t end = min(soff[s + 1], e0 + 4);
+    int64_t end = min(e0 + 4, soff[nseg]);
     for (int64_t k = e0; k < end; ++k) {
+      while (s + 1 < nseg && k >= soff[s + 1]) ++s;
+      float lr = slr[s], wd = swd[s];
+      if (lr == 0.f) continue;
       float gg = g[k] + wd * p[k];
       float vprev = v[k];
       float vnew = mu * vprev + lr * gg;
@@ -491,11 +501,11 @@ __global__ void adam_update_multi_kernel(
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
        i < total4; i += (int64_t)gridDim.x * blockDim.x) {
     int64_t e0 = i * 4;
-    while (s + 1 < nseg && e0 >= soff[s + 1]) ++s;
-    float lr = slr[s], wd = swd[s];
-    if (lr == 0.f) continue;
-    int64_t end = min(soff[s + 1], e0 + 4);
+    int64_t end = min(e0 + 4, soff[nseg]);
     for (int64_t k = e0; k < end; ++k) {
+      while (s + 1 < nseg && k >= soff[s + 1]) ++s;
+      float lr = slr[s], wd = swd[s];
+      if (lr == 0.f) continue;
       float gg = g[k] + wd * p[k];
       float mm = b1 * m[k] + (1.f - b1) * gg;
       float vv = b2 * v[k] + (1.f - b2) * gg * gg;

@@ -84,6 +84,24 @@ rules, one step at a time from the state the route itself emitted:
  backward   the loop route, which stores it as bf16; dc carried in float64
             with cont*gf*(tol + 4e*mag); dxg as the LSTM-unit dgates; dwhc
             (TN+4)e(|dxg|^T @ |h_in|).
+
+The fused whole-arena solver updates are bounded in _solver_update_cases.py
+(rules B1 and B3; no fast-math flag in the build, so sqrtf and the fp32
+divide are correctly rounded and cost one e each, not the I of B4):
+
+ Updates    every element with the lr / wd of the segment that owns it
+            (torch.bucketize on the offsets), gg = g + wd p; c e T with c
+            the roundings on a term's longest path plus one:
+            SGD v' = mu v + lr gg: 5e(mu|v| + lr(|g| + wd|p|)) = 5e T_v;
+            p' = p - v': 6e(|p| + T_v).  Nesterov v' as SGD;
+            p' = p - ((1+mu)v' - mu v): 9e(|p| + (1+mu)T_v + mu|v|).
+            Adam m' = b1 m + (1-b1)gg: 6e T_m, T_m = b1|m| + (1-b1)(|g| +
+            wd|p|); v' = b2 v + (1-b2)gg^2: 9e(b2 v + (1-b2)(|g| + wd|p|)^2);
+            p' = p - lr m'/(sqrt(v') + eps): the exact one-sided change of
+            the root under tol_v, 8e on the quotient's T and 2e(|p| + Tq),
+            about 16.5e(|p| + lr T_m/(sqrt(v') + eps)) in all.  A frozen
+            segment (lr == 0) keeps p, v, m and the shadow bit for bit;
+            elsewhere the shadow == bf16(p') of the p' the kernel wrote.
 """
 
 import torch

@@ -50,6 +50,14 @@ void gemm_conv_dw(const void* A, const void* X, float* C,
                   const void* zpage, int M, int N, int K, int lda, int ldc,
                   int store_mode, int splitk, float alpha, float* db,
                   const int* geom, hipStream_t stream);
+int gemm_conv_dw_grouped(const void* A, const void* X, float* C,
+                         const void* zpage, int M, int N, int K, int lda,
+                         int ldc, int splitk, float alpha, const int* geom,
+                         int G, hipStream_t stream);
+int conv_dw_splits(int K, int splitk);
+void dw_slab_finalize(const float* slabs, int splits, float* arena,
+                      int Kout, int Cg, int R, int S, int st, int Kpad,
+                      bool accumulate, int blocks, hipStream_t stream);
 void gemm_conv_fwd_sc(const void* X, const void* B, void* C,
                       const float* bias, int M, int N, int K, int ldb,
                       int ldc, bool relu, const int* geom,
@@ -470,6 +478,68 @@ void py_gemm_conv_dw(Tensor A, Tensor X, Tensor C,
                        zpage.data_ptr(), (int)M, (int)N, (int)K, (int)lda, (int)ldc,
                        (int)store_mode, (int)splitk, (float)alpha, dbp,
                        g, cur_stream());
+}
+
+// All G groups' dW GEMMs in one launch, split-K into plain-stored slabs
+// C[splits][G*M][ldc] (one split: C is the result).  Returns the slab
+// count for dw_slab_finalize, or 0 when nothing was launched because the
+// operands miss the DMA kernel's gate (the caller falls back, loudly or
+// to the per-group route).
+int64_t py_gemm_conv_dw_grouped(Tensor A, Tensor X, Tensor C, Tensor zpage,
+                                int64_t M, int64_t N, int64_t K,
+                                int64_t lda, int64_t ldc, int64_t splitk,
+                                double alpha, std::vector<int64_t> geom,
+                                int64_t G) {
+  CHECK_CUDA(A); CHECK_BF16(A); CHECK_CUDA(X); CHECK_BF16(X);
+  CHECK_CUDA(C); CHECK_F32(C);
+  CHECK_CUDA(zpage); CHECK_BF16(zpage);
+  TORCH_CHECK(zpage.numel() >= 8, "zpage must hold 16 zero bytes");
+  TORCH_CHECK(geom.size() == 14, "geom must have 14 ints");
+  int g[14];
+  for (int i = 0; i < 14; ++i) g[i] = (int)geom[i];
+  TORCH_CHECK(G >= 1 && G <= 65535 && M > 0 && N > 0 && K > 0,
+              "gemm_conv_dw_grouped: bad sizes");
+  TORCH_CHECK(lda >= G * M && ldc >= N,
+              "gemm_conv_dw_grouped: row strides shorter than the rows");
+  // channel windows of all groups inside the input's C channels
+  TORCH_CHECK(geom[11] >= 0 && geom[11] + G * geom[12] <= geom[2],
+              "gemm_conv_dw_grouped: group channel windows exceed C");
+  int64_t splits = cosamd::conv_dw_splits((int)K, (int)splitk);
+  TORCH_CHECK(C.is_contiguous() && C.numel() >= splits * G * M * ldc,
+              "gemm_conv_dw_grouped: C smaller than splits x G*M x ldc");
+  return cosamd::gemm_conv_dw_grouped(
+      A.data_ptr(), X.data_ptr(), C.data_ptr<float>(), zpage.data_ptr(),
+      (int)M, (int)N, (int)K, (int)lda, (int)ldc, (int)splitk, (float)alpha,
+      g, (int)G, cur_stream());
+}
+
+// st < 2: plain column map; st >= 2: the space-to-depth map.  blocks: 0 =
+// the kernel's own grid, > 0 forces it.
+void py_dw_slab_finalize(Tensor slabs, int64_t splits, Tensor arena,
+                         int64_t Kout, int64_t Cg, int64_t R, int64_t S,
+                         int64_t st, int64_t Kpad, bool accumulate,
+                         int64_t blocks) {
+  CHECK_CUDA(slabs); CHECK_F32(slabs); CHECK_CUDA(arena); CHECK_F32(arena);
+  int64_t ncol = R * S * Cg;
+  if (st >= 2)
+    ncol = ((R + st - 1) / st) * ((S + st - 1) / st) * st * st * Cg;
+  TORCH_CHECK(splits >= 1 && Kout > 0 && Cg > 0 && R > 0 && S > 0,
+              "dw_slab_finalize: bad sizes");
+  TORCH_CHECK(slabs.is_contiguous() && Kpad >= ncol &&
+              slabs.numel() >= splits * Kout * Kpad,
+              "dw_slab_finalize: slabs smaller than splits x Kout x Kpad");
+  // the kernel reads four columns with one 16-byte load
+  TORCH_CHECK(ncol % 4 == 0 && Kpad % 4 == 0 &&
+              (uintptr_t)slabs.data_ptr() % 16 == 0,
+              "dw_slab_finalize needs ncol % 4 == 0, Kpad % 4 == 0 and "
+              "16-byte aligned slabs");
+  TORCH_CHECK(blocks >= 0 && blocks <= 65535, "dw_slab_finalize: blocks");
+  TORCH_CHECK(arena.is_contiguous() && arena.numel() == Kout * Cg * R * S,
+              "dw_slab_finalize: arena is not [Kout][Cg][R][S]");
+  cosamd::dw_slab_finalize(slabs.data_ptr<float>(), (int)splits,
+                           arena.data_ptr<float>(), (int)Kout, (int)Cg,
+                           (int)R, (int)S, (int)st, (int)Kpad, accumulate,
+                           (int)blocks, cur_stream());
 }
 
 void py_relu_colsum_bwd(Tensor y, Tensor dy, Tensor dx, Tensor db,
@@ -1076,6 +1146,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_conv_dw", &py_gemm_conv_dw);
   m.def("gemm_conv_fwd_sc", &py_gemm_conv_fwd_sc);
   m.def("gemm_conv_dw_sc", &py_gemm_conv_dw_sc);
+  m.def("gemm_conv_dw_grouped", &py_gemm_conv_dw_grouped);
+  m.def("dw_slab_finalize", &py_dw_slab_finalize);
   m.def("im2col", &py_im2col);
   m.def("bn_stats", [](Tensor x, Tensor sum, Tensor sq, int64_t rows,
                        int64_t C) {

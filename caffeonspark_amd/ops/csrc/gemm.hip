@@ -1191,13 +1191,33 @@ __device__ __forceinline__ void wait_frags_tr(bf16x4 (&a)[4][2],
 // per tile at any depth, and every DMA always issues — tiles past the
 // split's end fetch the zero page — so the counted wait is exact for any
 // tile count >= 1 (pipelined_loop needs >= 2 and a power-of-two ring).
+//
+// Groups and slabs: blockIdx.z is the convolution group — A advances by
+// gs_a columns of dy, the channel window by gs_c0 and C by gs_c floats per
+// group — and with slab != 0 split blockIdx.y plain-stores (STORE 1) its
+// tile into slab blockIdx.y of a [splits][rows][ldc] buffer that
+// dw_slab_finalize (repack.hip) sums in split order: no atomics, no zero
+// fill.  Every split has at least one K tile (split_k), so every slab
+// element the finalize reads is stored by exactly one block.  Single-group
+// launches pass zero strides and slab 0.
+//
+// Rows beyond M: a wave reads and multiplies only the nfm 16-row fragments
+// of its 64-row band that start below M (conv1's M = 96 leaves the lower
+// band half empty).  nfm is wave-uniform and kept in an SGPR, so the
+// branches are scalar and the transposed reads still see EXEC all ones;
+// staging, the counted wait and the barrier stay unconditional.
 template <int STORE, int DEPTH>
 __global__ __launch_bounds__(WNT, DEPTH <= 3 ? 4 : 2)
 void gemm_conv_dw_tr_kernel(
     const bf16* __restrict__ A, const bf16* __restrict__ X,
     const bf16* __restrict__ zpage, float* __restrict__ C, int M, int N,
-    int K, int lda, int ldc, int ksplit, float alpha, CGeom gm) {
+    int K, int lda, int ldc, int ksplit, float alpha, CGeom gm, int gs_a,
+    int gs_c0, int64_t gs_c, int64_t slab) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[DEPTH * TR_STAGE];
+
+  A += (int64_t)blockIdx.z * gs_a;
+  gm.c0 += blockIdx.z * gs_c0;
+  C += blockIdx.z * gs_c + blockIdx.y * slab;
 
   Tile t = decode_tile<WBN>(M, N);
   int tile_m = t.tile_m, tile_n = t.tile_n;
@@ -1295,53 +1315,78 @@ void gemm_conv_dw_tr_kernel(
 
   f32x4 acc[4][4] = {};
 
+  // fragments of this wave's band that start below M (0..4), in an SGPR
+  int nfm = __builtin_amdgcn_readfirstlane(
+      min(4, max(0, (M - tile_m - wm * 64 + 15) >> 4)));
+  // outside the loop: a skipped fragment keeps its (unused) zeros
+  bf16x4 ar[4][2] = {}, br[4][2] = {};
+
   constexpr int PF = DEPTH - 1;          // tiles in flight ahead
   constexpr int VMCNT = 3 * (PF - 1);    // 3 DMAs per wave per tile
   int tiles = (k_end - k_begin + BK - 1) / BK;
 #pragma unroll
   for (int p = 0; p < PF; ++p) stage(p, k_begin + p * BK);
-  int cur = 0;                           // ring slot of tile i
-  for (int i = 0; i < tiles; ++i) {
-    wait_vmcnt<VMCNT>();                 // this wave's part of tile i landed
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();        // everyone's did; tile i-1 is read
-    int nxt = cur == 0 ? DEPTH - 1 : cur - 1;   // (i + PF) % DEPTH
-    stage(nxt, k_begin + (i + PF) * BK);
-    int img = cur * TR_STAGE;            // multiple of 128: keeps the XOR
-    bf16x4 ar[4][2], br[4][2];
+  // The loop exists twice: FULL (every fragment valid, the common case)
+  // is straight-line code with no test of nfm in it; the other tests
+  // nfm per fragment.  One copy with the tests cost the full bands of
+  // every layer a taken branch per fragment per tile.
+  auto k_loop = [&](auto full) {
+    constexpr bool FULL = decltype(full)::value;
+    int cur = 0;                         // ring slot of tile i
+    for (int i = 0; i < tiles; ++i) {
+      wait_vmcnt<VMCNT>();               // this wave's part of tile i landed
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_barrier();      // everyone's did; tile i-1 is read
+      int nxt = cur == 0 ? DEPTH - 1 : cur - 1;   // (i + PF) % DEPTH
+      stage(nxt, k_begin + (i + PF) * BK);
+      int img = cur * TR_STAGE;          // multiple of 128: keeps the XOR
+      if (FULL || nfm > 0) {
 #pragma unroll
-    for (int f = 0; f < 4; ++f)
+        for (int f = 0; f < 4; ++f)
 #pragma unroll
-      for (int h = 0; h < 2; ++h)
-        br[f][h] = ds_read_tr16(lds0 + ((img + b_addr[h]) ^ (f << 5)));
+          for (int h = 0; h < 2; ++h)
+            br[f][h] = ds_read_tr16(lds0 + ((img + b_addr[h]) ^ (f << 5)));
+      }
 #pragma unroll
-    for (int f = 0; f < 4; ++f)
+      for (int f = 0; f < 4; ++f) {
+        if (FULL || f < nfm) {
 #pragma unroll
-      for (int h = 0; h < 2; ++h)
-        ar[f][h] = ds_read_tr16(lds0 + ((img + a_addr[h]) ^ (f << 5)));
-    wait_frags_tr(ar, br);
-    bf16x8 afrag[4], bfrag[4];
+          for (int h = 0; h < 2; ++h)
+            ar[f][h] = ds_read_tr16(lds0 + ((img + a_addr[h]) ^ (f << 5)));
+        }
+      }
+      wait_frags_tr(ar, br);
+      bf16x8 afrag[4], bfrag[4];
 #pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      afrag[f] = __builtin_shufflevector(ar[f][0], ar[f][1], 0, 1, 2, 3, 4,
-                                         5, 6, 7);
-      bfrag[f] = __builtin_shufflevector(br[f][0], br[f][1], 0, 1, 2, 3, 4,
-                                         5, 6, 7);
+      for (int f = 0; f < 4; ++f) {
+        afrag[f] = __builtin_shufflevector(ar[f][0], ar[f][1], 0, 1, 2, 3,
+                                           4, 5, 6, 7);
+        bfrag[f] = __builtin_shufflevector(br[f][0], br[f][1], 0, 1, 2, 3,
+                                           4, 5, 6, 7);
+      }
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int fm = 0; fm < 4; ++fm) {
+        if (FULL || fm < nfm) {
+#pragma unroll
+          for (int fn = 0; fn < 4; ++fn)
+            acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                afrag[fm], bfrag[fn], acc[fm][fn], 0, 0, 0);
+        }
+      }
+      __builtin_amdgcn_s_setprio(0);
+      cur = cur + 1 == DEPTH ? 0 : cur + 1;
     }
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int fm = 0; fm < 4; ++fm)
-#pragma unroll
-      for (int fn = 0; fn < 4; ++fn)
-        acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            afrag[fm], bfrag[fn], acc[fm][fn], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-    cur = cur + 1 == DEPTH ? 0 : cur + 1;
-  }
+  };
+  if (nfm == 4)
+    k_loop(std::true_type{});
+  else
+    k_loop(std::false_type{});
   wait_vmcnt<0>();                       // the zero-page tail DMAs
 
-  epilogue_f32<STORE, false, 4, 64>(acc, C, nullptr, M, N, ldc, tile_m,
-                                    tile_n, wm, wn, lane, 0, alpha);
+  if (nfm > 0)                           // else every row is beyond M
+    epilogue_f32<STORE, false, 4, 64>(acc, C, nullptr, M, N, ldc, tile_m,
+                                      tile_n, wm, wn, lane, 0, alpha);
 }
 
 // ------------------------------------------------------------------- host
@@ -1654,11 +1699,43 @@ void gemm_conv_dw(const void* A, const void* X, float* C,
   if (store_mode == 1 && sk.zblocks == 1)
     gemm_conv_dw_tr_kernel<1, DW_TR_DEPTH><<<grid, WNT, 0, stream>>>(
         (const bf16*)A, (const bf16*)X, (const bf16*)zpage, C, M, N, K, lda,
-        ldc, sk.ksplit, alpha, gm);
+        ldc, sk.ksplit, alpha, gm, 0, 0, 0, 0);
   else
     gemm_conv_dw_tr_kernel<2, DW_TR_DEPTH><<<grid, WNT, 0, stream>>>(
         (const bf16*)A, (const bf16*)X, (const bf16*)zpage, C, M, N, K, lda,
-        ldc, sk.ksplit, alpha, gm);
+        ldc, sk.ksplit, alpha, gm, 0, 0, 0, 0);
+}
+
+// The dW GEMMs of all G groups of a layer in one launch, split-K into
+// slabs: group g reads dy columns [g*M, (g+1)*M) and channels
+// [c0 + g*Cg, c0 + (g+1)*Cg), and split s of it plain-stores rows
+// [g*M, (g+1)*M) of slab s of C[splits][G*M][ldc] — for dw_slab_finalize
+// to sum.  With one split C is the result itself.  Returns the number of
+// slabs written (split_k may give fewer than splitk), or 0 when the
+// operands miss the DMA kernel's gate (gemm_conv_dw's, for every group)
+// or COS_DW_TR=0: nothing was launched and the caller takes the
+// per-group atomic route.
+int conv_dw_splits(int K, int splitk) { return split_k(K, splitk).zblocks; }
+
+int gemm_conv_dw_grouped(const void* A, const void* X, float* C,
+                         const void* zpage, int M, int N, int K, int lda,
+                         int ldc, int splitk, float alpha, const int* geom,
+                         int G, hipStream_t stream) {
+  const char* tr_e = getenv("COS_DW_TR");   // per call, as gemm_conv_dw
+  CGeom gm = make_geom(geom);
+  bool tr = !(tr_e && tr_e[0] == '0') && zpage != nullptr && G >= 1 &&
+            ((M | lda | gm.C | gm.c0 | gm.Cg | gm.Kcol) % 8 == 0) &&
+            (((uintptr_t)A | (uintptr_t)X) % 16 == 0);
+  if (!tr) return 0;
+  SplitK sk = split_k(K, splitk);
+  int mblocks = (M + BM - 1) / BM, nblocks = (N + WBN - 1) / WBN;
+  dim3 grid(mblocks * nblocks, sk.zblocks, G);
+  int64_t rows = (int64_t)G * M;
+  gemm_conv_dw_tr_kernel<1, DW_TR_DEPTH><<<grid, WNT, 0, stream>>>(
+      (const bf16*)A, (const bf16*)X, (const bf16*)zpage, C, M, N, K, lda,
+      ldc, sk.ksplit, alpha, gm, M, gm.Cg, (int64_t)M * ldc,
+      sk.zblocks > 1 ? rows * ldc : 0);
+  return sk.zblocks;
 }
 
 void gemm_bf16(const void* A_, const void* B_, void* C, const float* bias,

@@ -105,6 +105,136 @@ def _splitk_dw(M: int, N: int, K: int, implicit: bool) -> int:
     return _splitk_tt(M, N, K, 256 if tr else 448)
 
 
+# BK of gemm.hip, the K extent of one staged tile: split_k() there rounds
+# a split to whole tiles and _split_count mirrors it (a disagreement is not
+# silent: _conv_dw_slab compares the kernel's slab count with the plan's)
+_GEMM_BK = 32
+
+
+def _split_count(K: int, splitk: int) -> int:
+    """Splits split_k() in gemm.hip makes of a request for `splitk`: K per
+    split rounded up to whole K tiles (_GEMM_BK wide), so every split has
+    at least one tile and none is empty.  A fixed point: asking for the
+    result gives the result."""
+    ks = -(-K // max(1, splitk))
+    ks = -(-ks // _GEMM_BK) * _GEMM_BK
+    return -(-K // ks)
+
+
+# Below this many slab bytes a layer keeps the legacy route.  The slab
+# route trades the atomics' traffic (slab bytes at about 1.3 TB/s) for a
+# finalize whose cost has a floor of about 10 us (a chain of `splits`
+# dependent-latency loads over few threads).  Only the two ends are
+# measured (profiles/alexnet_1gpu_dw_grouped.md): every AlexNet layer (22
+# to 32 MB) is faster on the slab route, CIFAR-10 quick's two layers (5 and
+# 2.5 MB) were 4 us a step slower on it.  16 MB is interpolated from those
+# two estimates, not a measured crossover; nothing between 5 and 22 MB was
+# timed on its own, and several GoogLeNet layers lie in that range.
+_DW_SLAB_MIN_BYTES = 16 << 20
+
+
+def conv_dw_plan(G, Kg, Kpad, NPQ, aligned=True):
+    """(route, splits, slab_bytes) of a bf16 conv layer's weight-gradient
+    GEMMs dw_g[Kg, Kpad] = dy_g[NPQ, Kg]^T col_g[NPQ, Kpad], g < G.
+
+    route "slab": ONE launch of gemm_conv_dw_tr_kernel over all G groups,
+    each split plain-storing its tile into its own slab, then ONE
+    dw_slab_finalize that sums the slabs in split order and writes the
+    caffe-layout gradient — no atomics, no zero fill, no separate unpack,
+    the same bits on every run.  route "legacy": a launch per group with
+    atomic split-K into a zeroed buffer, then dw_unpack_*; taken when the
+    operands miss the DMA kernel's gate (`aligned` false), with
+    COS_DW_TR=0, COS_DW_TT=0 or COS_FUSE_DB=1, when the slabs would hold
+    less than _DW_SLAB_MIN_BYTES, and with COS_DW_SLAB=0 (the A/B switch;
+    COS_DW_SLAB=1 takes the slab route at any size).  The environment is
+    read on every call.
+
+    splits (per group, as resolved by split_k) aims for one block per CU
+    over ALL groups — 256 blocks, COS_SPLITK_TARGET overrides — under
+    _splitk_tt's caps: no split below K = 1024, at least 512 K per split.
+    For G = 1 that is _splitk_dw's count; a two-group layer gets half the
+    splits per group the per-group launches used, so each block runs
+    twice the K tiles in front of its epilogue.  For "legacy" splits is
+    what each per-group launch resolves to.  slab_bytes: the fp32
+    [splits][G*Kg][Kpad] workspace, 0 when splits == 1 (the single slab
+    is the GEMM's ordinary output) or the route is "legacy"."""
+    env = os.environ.get
+    mode = env("COS_DW_SLAB", "")
+    slab = aligned and mode != "0" and \
+        env("COS_DW_TR", "1") != "0" and \
+        bool(int(env("COS_DW_TT", "1"))) and \
+        not bool(int(env("COS_FUSE_DB", "0")))
+    legacy = ("legacy", _split_count(
+        NPQ, _splitk_dw(Kg, Kpad, NPQ, aligned)), 0)
+    if not slab:
+        return legacy
+    # 128 x 256 output tiles (both callers come here with Kpad > 128)
+    mb, nb = (Kg + 127) // 128, (Kpad + 255) // 256
+    if NPQ < 1024:
+        want = 1
+    else:
+        target = int(env("COS_SPLITK_TARGET", 256))
+        want = max(1, min(target // max(1, G * mb * nb), NPQ // 512))
+    splits = _split_count(NPQ, want)
+    slab_bytes = splits * G * Kg * Kpad * 4 if splits > 1 else 0
+    if slab_bytes < _DW_SLAB_MIN_BYTES and mode != "1":
+        return legacy
+    return "slab", splits, slab_bytes
+
+
+_dw_slabs = {}
+
+
+def _dw_slab_buf(numel, device):
+    """The first `numel` floats of the ONE slab workspace all layers of a
+    device share: a layer's finalize has read its slabs before the next
+    layer's GEMM, on the same stream, writes them.  Never zeroed — every
+    element the finalize reads is stored by exactly one block each step.
+    It grows to the largest layer seen (AlexNet: 32 MB) and a replaced
+    buffer is retired, not freed: a captured hipGraph may hold its
+    address."""
+    t = _dw_slabs.get(device.index)
+    if t is None or t.numel() < numel:
+        if t is not None:
+            _scratch["retired"].append(t)
+        t = torch.empty((numel,), dtype=torch.float32, device=device)
+        _dw_slabs[device.index] = t
+    return t[:numel]
+
+
+def _conv_dw_slab(dy0, xl, ld_dy, geom, G, Kg, Kpad, NPQ, splits,
+                  arena, Cg, R, S, st=0):
+    """The "slab" route of conv_dw_plan: grouped GEMM into the shared
+    slab workspace, then the ordered reduce fused with the unpack into
+    `arena` ([G*Kg][Cg][R][S] fp32, overwritten)."""
+    Kout = G * Kg
+    if splits > 1:
+        slabs = _dw_slab_buf(splits * Kout * Kpad, xl.device).view(
+            splits, Kout, Kpad)
+    else:
+        slabs = torch.empty((1, Kout, Kpad), dtype=torch.float32,
+                            device=xl.device)
+    wrote = _ext.gemm_conv_dw_grouped(dy0, xl, slabs, _zpage(xl.device),
+                                      Kg, Kpad, NPQ, ld_dy, Kpad, splits,
+                                      1.0, geom, G)
+    if wrote != splits:
+        raise RuntimeError(
+            f"conv dW slab route planned {splits} slabs, kernel wrote "
+            f"{wrote} (0: operands miss the DMA kernel's gate)")
+    _ext.dw_slab_finalize(slabs, wrote, arena, Kout, Cg, R, S, st, Kpad,
+                          False, 0)
+    return arena
+
+
+def _dw_target(dw_out, shape, device):
+    """dw_out when it is a dense fp32 tensor of `shape` (the solver's
+    arena slice), else a fresh one."""
+    if dw_out is not None and dw_out.dtype == torch.float32 \
+            and dw_out.is_contiguous() and tuple(dw_out.shape) == shape:
+        return dw_out
+    return torch.empty(shape, dtype=torch.float32, device=device)
+
+
 def _pad128(n: int) -> int:
     return (n + 127) // 128 * 128
 
@@ -588,8 +718,17 @@ def _conv_dw_s2d(ctx, dyg, ld_dy, dw_out):
     st, Rp, Sp, Cp, Hp, Wp, Kcol_s, Kpad_s = ctx["s2d"]
     Kout, NPQ = Kg, N * P * Q
     xs = ctx["xs2d"]
-    sk_tt = _splitk_dw(Kout, Kpad_s, NPQ,
-                       (Cp | Kout | ld_dy | Kcol_s) % 8 == 0)
+    geom = [Hp, Wp, Cp, P, Q, 1, 1, 0, 0, 1, Sp, 0, Cp, Kcol_s]
+    dw_tr = (Cp | Kout | ld_dy | Kcol_s) % 8 == 0
+    route, splits, _ = conv_dw_plan(
+        1, Kout, Kpad_s, NPQ,
+        dw_tr and (dyg.data_ptr() | xs.data_ptr()) % 16 == 0)
+    ctx["dw_route"] = route
+    if route == "slab":
+        dw = _dw_target(dw_out, (Kout, C, R, S), xs.device)
+        return _conv_dw_slab(dyg, xs, ld_dy, geom, 1, Kout, Kpad_s, NPQ,
+                             splits, dw, C, R, S, st)
+    sk_tt = _splitk_dw(Kout, Kpad_s, NPQ, dw_tr)
     if sk_tt == 1:
         dwp = torch.empty((Kout, Kpad_s), dtype=torch.float32,
                           device=xs.device)
@@ -597,7 +736,6 @@ def _conv_dw_s2d(ctx, dyg, ld_dy, dw_out):
     else:
         dwp = _scratch_buf((Kout, Kpad_s), torch.float32, xs.device)
         store_dw = 2
-    geom = [Hp, Wp, Cp, P, Q, 1, 1, 0, 0, 1, Sp, 0, Cp, Kcol_s]
     _ext.gemm_conv_dw(dyg, xs, dwp, None, _zpage(xs.device), Kout, Kpad_s,
                       NPQ, ld_dy, Kpad_s, store_dw, sk_tt, 1.0, geom)
     if dw_out is not None and dw_out.dtype == torch.float32 \
@@ -742,8 +880,22 @@ def conv2d_backward(x, w, dy, stride, pad, dilation, groups,
     if fuse_db:
         db = db_out if db_out is not None \
             else _scratch_buf((Kout,), torch.float32, dy.device)
+    dw_route = "legacy"
+    if need_dw and not s2d and dw_implicit:
+        dw_route, dw_splits, _ = conv_dw_plan(
+            G, Kg, Kpad, NPQ,
+            (C | Cg | Kg | ld_dy | Kcol) % 8 == 0 and
+            (_dyg(0).data_ptr() | ctx["xl"].data_ptr()) % 16 == 0)
+        ctx["dw_route"] = dw_route
     if need_dw and s2d:
         dw = _conv_dw_s2d(ctx, _dyg(0), ld_dy, dw_out)
+    elif need_dw and dw_route == "slab":
+        # all groups in one launch, slab split-K, reduce fused with the
+        # unpack to caffe layout (conv_dw_plan)
+        geom = [H, W, C, P, Q, sh, sw, ph, pw, dil, S, 0, Cg, Kcol]
+        dw = _conv_dw_slab(
+            _dyg(0), ctx["xl"], ld_dy, geom, G, Kg, Kpad, NPQ, dw_splits,
+            _dw_target(dw_out, (Kout, Cg, R, S), dy.device), Cg, R, S)
     elif need_dw:
         # dw[kout][kpad] = sum_npq dy[npq][kout] * col[npq][kpad].
         # fused trans/trans dw (u32 k-pair staged; round 2): reads dy2/col

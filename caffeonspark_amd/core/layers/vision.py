@@ -428,7 +428,8 @@ class LRNLayer(Layer):
 
     def forward(self, bottom, top):
         y, self._scale = ops.lrn_forward(bottom[0].data, self.local_size,
-                                         self.alpha, self.beta, self.k)
+                                         self.alpha, self.beta, self.k,
+                                         keep_scale=False)
         top[0].data = y
         return 0.0
 

@@ -141,6 +141,9 @@ void lrn_fwd(const void* x, void* y, float* scale, int64_t npix, int C,
 void lrn_bwd(const void* x, const void* y, const float* scale, const void* dy,
              void* dx, void* ratio, int64_t npix, int C, int local_size,
              float alpha, float beta, hipStream_t stream);
+void lrn_bwd_fused(const void* x, const void* dy, void* dx, int64_t npix,
+                   int C, int local_size, float alpha, float beta, float k,
+                   int max_blocks, hipStream_t stream);
 void relu_fwd(const void* x, void* y, float slope, int64_t n,
               hipStream_t stream);
 void relu_bwd(const void* y, const void* dy, void* dx, float slope, int64_t n,
@@ -683,11 +686,18 @@ void py_avgpool_bwd(Tensor dy, Tensor dx, int64_t N, int64_t H, int64_t W,
                       sh, sw, ph, pw, cur_stream());
 }
 
-void py_lrn_fwd(Tensor x, Tensor y, Tensor scale, int64_t npix, int64_t C,
-                int64_t local_size, double alpha, double beta, double k) {
-  CHECK_F32(scale);
-  cosamd::lrn_fwd(x.data_ptr(), y.data_ptr(), scale.data_ptr<float>(), npix,
-                  C, local_size, alpha, beta, k, cur_stream());
+// scale = None: y only, for the fused backward that recomputes the scale
+void py_lrn_fwd(Tensor x, Tensor y, c10::optional<Tensor> scale, int64_t npix,
+                int64_t C, int64_t local_size, double alpha, double beta,
+                double k) {
+  float* sp = nullptr;
+  if (scale.has_value()) {
+    CHECK_F32((*scale));
+    TORCH_CHECK(scale->numel() >= npix * C, "lrn_fwd: scale too small");
+    sp = scale->data_ptr<float>();
+  }
+  cosamd::lrn_fwd(x.data_ptr(), y.data_ptr(), sp, npix, C, local_size, alpha,
+                  beta, k, cur_stream());
 }
 
 void py_lrn_bwd(Tensor x, Tensor y, Tensor scale, Tensor dy, Tensor dx,
@@ -696,6 +706,42 @@ void py_lrn_bwd(Tensor x, Tensor y, Tensor scale, Tensor dy, Tensor dx,
   cosamd::lrn_bwd(x.data_ptr(), y.data_ptr(), scale.data_ptr<float>(),
                   dy.data_ptr(), dx.data_ptr(), ratio.data_ptr(), npix, C,
                   local_size, alpha, beta, cur_stream());
+}
+
+// One-pass LRN backward: dense [npix][C] bf16 x, dy -> dx.  Threads read
+// their neighbours' channel octets of x and dy, so dx may overlap neither.
+// max_blocks 0 = launcher-sized grid.
+void py_lrn_bwd_fused(Tensor x, Tensor dy, Tensor dx, int64_t npix, int64_t C,
+                      int64_t local_size, double alpha, double beta, double k,
+                      int64_t max_blocks) {
+  CHECK_CUDA(x); CHECK_CUDA(dy); CHECK_CUDA(dx);
+  CHECK_BF16(x); CHECK_BF16(dy); CHECK_BF16(dx);
+  TORCH_CHECK(C > 0 && C % 8 == 0, "lrn_bwd_fused needs C % 8 == 0");
+  TORCH_CHECK(local_size >= 1 && local_size <= 9 && local_size % 2 == 1,
+              "lrn_bwd_fused needs an odd local_size <= 9");
+  TORCH_CHECK(npix >= 0 && x.numel() == npix * C && dy.numel() == npix * C &&
+              dx.numel() == npix * C,
+              "lrn_bwd_fused: tensors are not npix x C");
+  auto dense = [](const Tensor& t) {
+    return t.is_contiguous() ||
+           (t.dim() == 4 && t.is_contiguous(at::MemoryFormat::ChannelsLast));
+  };
+  TORCH_CHECK(dense(x) && dense(dy) && dense(dx),
+              "lrn_bwd_fused needs dense [npix][C] tensors");
+  auto addr = [](const Tensor& t) { return (uintptr_t)t.data_ptr(); };
+  TORCH_CHECK(addr(x) % 16 == 0 && addr(dy) % 16 == 0 && addr(dx) % 16 == 0,
+              "lrn_bwd_fused needs 16-byte aligned tensors");
+  uintptr_t bytes = (uintptr_t)(npix * C) * 2;
+  auto overlaps = [&](const Tensor& t) {
+    uintptr_t a = addr(dx), b = addr(t);
+    return a < b + bytes && b < a + bytes;
+  };
+  TORCH_CHECK(!overlaps(x) && !overlaps(dy),
+              "lrn_bwd_fused: dx must not alias x or dy");
+  TORCH_CHECK(max_blocks >= 0 && max_blocks <= 65535, "max_blocks");
+  cosamd::lrn_bwd_fused(x.data_ptr(), dy.data_ptr(), dx.data_ptr(), npix,
+                        (int)C, (int)local_size, alpha, beta, k,
+                        (int)max_blocks, cur_stream());
 }
 
 void py_relu_fwd(Tensor x, Tensor y, double slope) {
@@ -1200,6 +1246,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("avgpool_bwd", &py_avgpool_bwd);
   m.def("lrn_fwd", &py_lrn_fwd);
   m.def("lrn_bwd", &py_lrn_bwd);
+  m.def("lrn_bwd_fused", &py_lrn_bwd_fused, py::arg("x"), py::arg("dy"),
+        py::arg("dx"), py::arg("npix"), py::arg("C"), py::arg("local_size"),
+        py::arg("alpha"), py::arg("beta"), py::arg("k"),
+        py::arg("max_blocks") = 0);
   m.def("relu_fwd", &py_relu_fwd);
   m.def("relu_bwd", &py_relu_bwd);
   m.def("dropout_fwd", &py_dropout_fwd);

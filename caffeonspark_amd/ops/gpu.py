@@ -1830,7 +1830,17 @@ def global_avgpool_backward(x_shape, dy):
 
 # -------------------------------------------------------------------- LRN
 
-def lrn_forward(x, local_size, alpha, beta, k):
+def _lrn_fused() -> bool:
+    """The one-pass backward that recomputes scale, y and ratio in registers
+    (lrn_bwd_fused_kernel).  COS_LRN_FUSED=0 is the A/B switch back to the
+    two-pass route over a stored fp32 scale; it is read here only."""
+    return os.environ.get("COS_LRN_FUSED", "1") != "0"
+
+
+def lrn_forward(x, local_size, alpha, beta, k, keep_scale=True):
+    """Returns (y, pack); pack[0] is the fp32 scale (NHWC).  keep_scale=False
+    leaves it None where the backward does not read it: on the fused route.
+    The pack carries k, which the fused backward needs to rebuild the scale."""
     _check_bf16(x, "lrn input")
     N, C, H, W = x.shape
     if C % 8 or local_size > 9:
@@ -1838,9 +1848,12 @@ def lrn_forward(x, local_size, alpha, beta, k):
         return reference.lrn_forward(x, local_size, alpha, beta, k)
     xl = _cl(x)
     y = torch.empty_like(xl)
-    scale = torch.empty((N, H, W, C), dtype=torch.float32, device=x.device)
+    scale = None
+    if keep_scale or not _lrn_fused():
+        scale = torch.empty((N, H, W, C), dtype=torch.float32,
+                            device=x.device)
     _ext.lrn_fwd(xl, y, scale, N * H * W, C, local_size, alpha, beta, k)
-    return y, (scale, xl)
+    return y, (scale, xl, k)
 
 
 def lrn_backward(x, y, scale_pack, dy, local_size, alpha, beta):
@@ -1848,8 +1861,15 @@ def lrn_backward(x, y, scale_pack, dy, local_size, alpha, beta):
     if C % 8 or local_size > 9:
         return reference.lrn_backward(x, y, scale_pack, dy, local_size,
                                       alpha, beta)
-    scale, xl = scale_pack
+    scale, xl, k = scale_pack
     dx = torch.empty_like(xl)
+    if _lrn_fused():
+        _ext.lrn_bwd_fused(xl, _cl(dy), dx, N * H * W, C, local_size, alpha,
+                           beta, k)
+        return dx
+    if scale is None:
+        raise RuntimeError("COS_LRN_FUSED=0 backward needs the forward's "
+                           "scale; the pack was made without one")
     ratio = torch.empty_like(xl)
     _ext.lrn_bwd(xl, _cl(y), scale, _cl(dy), dx, ratio, N * H * W, C,
                  local_size, alpha, beta)

@@ -179,9 +179,10 @@ def global_avgpool_backward(x_shape, dy):
 
 # ------------------------------------------------------------------------- LRN
 
-def lrn_forward(x, local_size, alpha, beta, k):
+def lrn_forward(x, local_size, alpha, beta, k, keep_scale=True):
     """Across-channel LRN (caffe): scale = k + alpha/n * sum_win x^2,
-    y = x * scale^-beta. Returns (y, scale) — scale reused in backward."""
+    y = x * scale^-beta. Returns (y, scale) — scale reused in backward, so
+    keep_scale (the GPU route's saving) is ignored here."""
     xf = x.float()
     sq = xf * xf
     pad = local_size // 2

@@ -81,6 +81,15 @@ void d2s_pack_weight(const void* src, void* dst, int Ci, int Co, int R,
 void d2s_unpack(const void* z, void* y, int N, int Co, int Ho, int Wo,
                 int st, int ph, int pw, int Hp, int Wp, int64_t sN,
                 int64_t sC, int64_t sH, int64_t sW, hipStream_t stream);
+void dwconv_fwd(const void* x, const void* w, const float* bias, void* y,
+                int ldy, bool relu, const int* geom, hipStream_t stream);
+void dwconv_dx(const void* dy, int ld_dy, const void* w, void* dx,
+               bool accumulate, const int* geom, hipStream_t stream);
+int dwconv_dw_slabs(int64_t NPQ, int want);
+int dwconv_dw(const void* dy, int ld_dy, const void* x, float* slabs,
+              int want, const int* geom, hipStream_t stream);
+void dwconv_dw_finalize(const float* slabs, int nslabs, float* dw, int C,
+                        int RS, hipStream_t stream);
 void data_transform(const void* src, int64_t src_bytes, const int64_t* table,
                     const int64_t* table_host, int N, const float* mean,
                     int mean_mode, int64_t mean_numel, int mC, int mH,
@@ -978,6 +987,115 @@ void py_d2s_unpack(Tensor z, Tensor y, int64_t st, int64_t ph, int64_t pw,
                      cur_stream());
 }
 
+// ---- depthwise convolution (dwconv.hip).  geom = [N, H, W, C, P, Q, R, S,
+// sh, sw, ph, pw, dil]; x and dx are dense NHWC (channels-last 4-D tensors),
+// y and dy rows of C channels ld elements apart, w the caffe-layout
+// [C][1][R][S] bf16 weight.  Every extent a kernel touches is checked
+// against the tensor's storage here.
+struct DwcArgs { int g[13]; int64_t NPQ, NHW, C, RS; };
+
+DwcArgs dwc_args(const std::vector<int64_t>& geom) {
+  TORCH_CHECK(geom.size() == 13, "dwconv: geom must have 13 ints");
+  DwcArgs a;
+  for (int i = 0; i < 13; ++i) {
+    TORCH_CHECK(geom[i] >= 0 && geom[i] < (1ll << 31), "dwconv: bad geom");
+    a.g[i] = (int)geom[i];
+  }
+  a.C = geom[3];
+  a.NHW = geom[0] * geom[1] * geom[2];
+  a.NPQ = geom[0] * geom[4] * geom[5];
+  a.RS = geom[6] * geom[7];
+  return a;
+}
+
+int64_t dwc_span(const Tensor& t) {
+  return (int64_t)(t.storage().nbytes() / t.element_size()) -
+         t.storage_offset();
+}
+
+// dense NHWC activation of N*H*W rows (the tensor's own extent)
+void dwc_check_dense(const Tensor& t, int64_t rows, int64_t C,
+                     const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 &&
+              t.dim() == 4 && t.size(1) == C && t.numel() == rows * C &&
+              t.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "dwconv: ", what, " must be a dense channels-last bf16 "
+              "tensor of ", rows, " x ", C);
+}
+
+// rows of C channels, ld apart, starting at the tensor's data pointer
+void dwc_check_rows(const Tensor& t, int64_t rows, int64_t C, int64_t ld,
+                    const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 && ld >= C &&
+              ld < (1ll << 31) && (rows - 1) * ld + C <= dwc_span(t),
+              "dwconv: ", what, " does not hold ", rows, " rows of ", C,
+              " bf16 channels at stride ", ld);
+}
+
+void dwc_check_weight(const Tensor& w, const DwcArgs& a) {
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == at::kBFloat16 &&
+              w.is_contiguous() && w.numel() == a.C * a.RS,
+              "dwconv: weight must be contiguous bf16 [C][1][R][S]");
+}
+
+void py_dwconv_fwd(Tensor x, Tensor w, c10::optional<Tensor> bias, Tensor y,
+                   int64_t ldy, bool relu, std::vector<int64_t> geom) {
+  DwcArgs a = dwc_args(geom);
+  dwc_check_dense(x, a.NHW, a.C, "x");
+  dwc_check_weight(w, a);
+  dwc_check_rows(y, a.NPQ, a.C, ldy, "y");
+  const float* bp = nullptr;
+  if (bias.has_value()) {
+    CHECK_CUDA(bias.value()); CHECK_F32(bias.value());
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == a.C,
+                "dwconv_fwd: bias must be contiguous fp32 [C]");
+    bp = bias->data_ptr<float>();
+  }
+  cosamd::dwconv_fwd(x.data_ptr(), w.data_ptr(), bp, y.data_ptr(), (int)ldy,
+                     relu, a.g, cur_stream());
+}
+
+void py_dwconv_dx(Tensor dy, int64_t ld_dy, Tensor w, Tensor dx,
+                  bool accumulate, std::vector<int64_t> geom) {
+  DwcArgs a = dwc_args(geom);
+  dwc_check_rows(dy, a.NPQ, a.C, ld_dy, "dy");
+  dwc_check_weight(w, a);
+  dwc_check_dense(dx, a.NHW, a.C, "dx");
+  cosamd::dwconv_dx(dy.data_ptr(), (int)ld_dy, w.data_ptr(), dx.data_ptr(),
+                    accumulate, a.g, cur_stream());
+}
+
+// slabs: fp32 workspace of at least (resolved slab count) x R*S x C; returns
+// the number of slabs written (`want` resolved so that none is empty)
+int64_t py_dwconv_dw(Tensor dy, int64_t ld_dy, Tensor x, Tensor slabs,
+                     int64_t want, std::vector<int64_t> geom) {
+  DwcArgs a = dwc_args(geom);
+  dwc_check_rows(dy, a.NPQ, a.C, ld_dy, "dy");
+  dwc_check_dense(x, a.NHW, a.C, "x");
+  TORCH_CHECK(want >= 1 && want <= 65535 && a.NPQ > 0,
+              "dwconv_dw: bad slab count");
+  int64_t n = cosamd::dwconv_dw_slabs(a.NPQ, (int)want);
+  CHECK_CUDA(slabs); CHECK_F32(slabs);
+  TORCH_CHECK(slabs.is_contiguous() && slabs.numel() >= n * a.RS * a.C,
+              "dwconv_dw: workspace smaller than ", n, " slabs");
+  return cosamd::dwconv_dw(dy.data_ptr(), (int)ld_dy, x.data_ptr(),
+                           slabs.data_ptr<float>(), (int)want, a.g,
+                           cur_stream());
+}
+
+void py_dwconv_dw_finalize(Tensor slabs, int64_t nslabs, Tensor dw,
+                           int64_t C, int64_t RS) {
+  CHECK_CUDA(slabs); CHECK_F32(slabs); CHECK_CUDA(dw); CHECK_F32(dw);
+  TORCH_CHECK(nslabs >= 1 && C > 0 && RS > 0 && C * RS < (1ll << 31) &&
+              slabs.is_contiguous() && slabs.numel() >= nslabs * RS * C,
+              "dwconv_dw_finalize: workspace smaller than the slabs");
+  TORCH_CHECK(dw.is_contiguous() && dw.numel() == C * RS,
+              "dwconv_dw_finalize: dw is not [C][1][R][S]");
+  cosamd::dwconv_dw_finalize(slabs.data_ptr<float>(), (int)nslabs,
+                             dw.data_ptr<float>(), (int)C, (int)RS,
+                             cur_stream());
+}
+
 void py_dw_unpack_s2d(Tensor dwp, Tensor arena, int64_t Kout, int64_t Cg,
                       int64_t R, int64_t S, int64_t st, int64_t Kpad,
                       bool accumulate) {
@@ -1276,6 +1394,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("s2d_pack_weight", &py_s2d_pack_weight);
   m.def("d2s_pack_weight", &py_d2s_pack_weight);
   m.def("d2s_unpack", &py_d2s_unpack);
+  m.def("dwconv_fwd", &py_dwconv_fwd);
+  m.def("dwconv_dx", &py_dwconv_dx);
+  m.def("dwconv_dw", &py_dwconv_dw);
+  m.def("dwconv_dw_finalize", &py_dwconv_dw_finalize);
   m.def("data_transform", &py_data_transform);
   m.def("dw_unpack_s2d", &py_dw_unpack_s2d);
   m.def("lstm_persist_fwd", &py_lstm_persist_fwd);

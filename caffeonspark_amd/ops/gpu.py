@@ -408,6 +408,88 @@ def _dx_imp_ok(N, H, W, R, S, sh, sw, ph, pw, dil, Kg):
             and R * S * Kg < (1 << 20))
 
 
+def _dwc_ok(C, Kout, G, Cg, R, S, aligned):
+    """Gate of the direct depthwise kernels (csrc/dwconv.hip): one filter
+    per channel (channel multiplier 1), whole channel octets, filters up to
+    7x7, and `aligned` — every base pointer the kernels read or write with
+    16-byte accesses is 16-byte aligned and every row stride a multiple of
+    8 elements.  COS_DWC=0 (read on every call) sends these layers back to
+    the per-group GEMM loop."""
+    return (G == C == Kout and Cg == 1 and C % 8 == 0
+            and R <= 7 and S <= 7 and bool(aligned)
+            and os.environ.get("COS_DWC", "1") != "0")
+
+
+def _dwc_slabs(C, NPQ):
+    """NPQ slabs of the depthwise dW: about four blocks per CU over the
+    C/64 channel ranges, at most 256 slabs for the finalize to add, each
+    lane of a block (256 / octets position lanes) with eight rows or more;
+    one slab when NPQ is small."""
+    cb8 = min(C // 8, 8)
+    ranges = -(-(C // 8) // cb8)
+    return max(1, min(1024 // ranges, 256, NPQ // (256 // cb8 * 8)))
+
+
+def _dwc_geom(shape):
+    (N, C, H, W, P, Q, R, S, sh, sw, ph, pw, dil) = shape[:13]
+    return [N, H, W, C, P, Q, R, S, sh, sw, ph, pw, dil]
+
+
+def _conv2d_forward_dwc(xl, w, b, shape, ctx, relu, out_into):
+    (N, C, H, W, P, Q, R, S) = shape[:8]
+    y, y2, ldy = _conv_out(xl.device, N, C, P, Q, out_into)
+    bias_f = b.float().contiguous() if b is not None else None
+    # the caffe-layout weight as it stands: nothing packed, nothing cached
+    _ext.dwconv_fwd(xl, _as_bf16(w).contiguous(), bias_f, y2, ldy, relu,
+                    _dwc_geom(shape))
+    if ctx is not None:
+        ctx.update(dwc=True, col=None, xl=xl, is_1x1=False, implicit=False,
+                   implicit_sc=False, s2d=None, shape=shape, wr=None,
+                   w_ref=w)
+    return y
+
+
+def _conv2d_backward_dwc(ctx, w, dy, need_dx, need_dw, bias, dw_out, db_out,
+                         dx_into):
+    shape = ctx["shape"]
+    (N, C, H, W, P, Q, R, S) = shape[:8]
+    NPQ = N * P * Q
+    geom = _dwc_geom(shape)
+    xl = ctx["xl"]
+    # the fused-concat channel window is read through its row stride
+    ld_dy = _cl_slice_ld(dy)
+    if ld_dy is not None and ld_dy % 8 == 0 and dy.data_ptr() % 16 == 0:
+        dyl = dy
+    else:
+        dyl, ld_dy = _cl(dy), C
+        if dyl.data_ptr() % 16 != 0:
+            dyl = dyl.clone(memory_format=torch.channels_last)
+    dx = dw = db = None
+    if need_dw:
+        want = _dwc_slabs(C, NPQ)
+        slabs = _dw_slab_buf(want * R * S * C, dy.device)
+        wrote = _ext.dwconv_dw(dyl, ld_dy, xl, slabs, want, geom)
+        dw = _dw_target(dw_out, (C, 1, R, S), dy.device)
+        _ext.dwconv_dw_finalize(slabs, wrote, dw, C, R * S)
+    if bias:
+        # db_out = the solver's pre-zeroed arena slice (see conv2d_backward)
+        db = db_out if db_out is not None \
+            else _scratch_buf((C,), torch.float32, dy.device)
+        _ext.colsum(dyl, db, NPQ, C, ld_dy)
+    if need_dx:
+        dx_acc = dx_into is not None and \
+            dx_into.is_contiguous(memory_format=torch.channels_last) and \
+            dx_into.dtype == torch.bfloat16 and \
+            tuple(dx_into.shape) == (N, C, H, W) and \
+            dx_into.data_ptr() % 16 == 0
+        dx = dx_into if dx_acc else torch.empty(
+            (N, C, H, W), dtype=torch.bfloat16, device=dy.device,
+            memory_format=torch.channels_last)
+        _ext.dwconv_dx(dyl, ld_dy, _as_bf16(w).contiguous(), dx, dx_acc,
+                       geom)
+    return dx, dw, db
+
+
 def conv2d_forward(x, w, b, stride, pad, dilation, groups, ctx=None,
                    relu=False, out_into=None):
     _check_bf16(x, "conv input")
@@ -421,6 +503,18 @@ def conv2d_forward(x, w, b, stride, pad, dilation, groups, ctx=None,
     G = groups
     Kg = Kout // G
     Kcol = R * S * Cg
+    if _dwc_ok(C, Kout, G, Cg, R, S, True):
+        # depthwise: direct kernels instead of a GEMM per channel.  The
+        # alignment half of the gate needs the channels-last input and the
+        # output window, which only this class of layer pays for here
+        xl = _cl(x)
+        aligned = xl.data_ptr() % 16 == 0 and (out_into is None or (
+            out_into[0].shape[1] % 8 == 0 and out_into[1] % 8 == 0
+            and out_into[0].data_ptr() % 16 == 0))
+        if _dwc_ok(C, Kout, G, Cg, R, S, aligned):
+            return _conv2d_forward_dwc(
+                xl, w, b, (N, C, H, W, P, Q, R, S, sh, sw, ph, pw, dil, G,
+                           Cg, Kg, _pad8(Kcol), Kcol), ctx, relu, out_into)
     # implicit-im2col GEMM (round 2): stage the col operand straight
     # from the NHWC input inside the GEMM — the col matrix is never
     # materialized.  Needs 8-aligned channel octets (one (r,s) tap per
@@ -819,6 +913,9 @@ def conv2d_backward(x, w, dy, stride, pad, dilation, groups,
         ctx = ctx if ctx is not None else {}
         conv2d_forward(_cl(x), w, None, stride, pad, dilation, groups,
                        ctx=ctx)
+    if ctx.get("dwc"):
+        return _conv2d_backward_dwc(ctx, w, dy, need_dx, need_dw, bias,
+                                    dw_out, db_out, dx_into)
     (N, C, H, W, P, Q, R, S, sh, sw, ph, pw, dil, G, Cg, Kg, Kpad,
      Kcol) = ctx["shape"]
     col, wr = ctx["col"], ctx["wr"]

@@ -1,4 +1,4 @@
-"""Recurrent layers: LSTM (time-major), Embed.
+"""Recurrent layers: LSTM and RNN (time-major), Embed.
 
 Caffe's LSTM layer (used by the reference's LRCN captioning net,
 data/lrcn_cos.prototxt — SURVEY.md §5 "Long-context") consumes
@@ -328,6 +328,166 @@ class LSTMLayer(Layer):
                 dxs = (d_static @ self.weight(3).float()).to(x.dtype)
                 self.acc_blob_diff(bottom[2],
                                    dxs.reshape(bottom[2].data.shape), False)
+
+
+@register_layer("RNN")
+class RNNLayer(Layer):
+    """Caffe's plain tanh recurrence, time-major like LSTM:
+
+        h_t = tanh(W_hh (cont_t * h_{t-1}) + W_xh x_t + b_h [+ W_xsh x_static])
+        o_t = tanh(W_ho h_t + b_o)
+
+    Bottoms x [T,N,...], cont [T,N], optional x_static [N,...], and with
+    recurrent_param.expose_hidden h_0 [1,N,H]; tops o [T,N,H] and, exposed,
+    h_T [1,N,H].  Without expose_hidden every forward starts from h = 0.
+
+    Params (upstream snapshot order):
+      0: W_xh [H, D]   1: b_h [H]   (2: W_xsh [H, Ds] with x_static)
+      then W_hh [H, H], W_ho [H, H], b_o [H]
+
+    Everything but the recurrence is one large GEMM over all T steps
+    (ops.fc_forward / ops.fc_backward); the recurrence is
+    ops.rnn_seq_forward / rnn_seq_backward, on the bf16 GPU path the
+    batch-tile-resident kernels of ops/csrc/rnn_seq.hip."""
+
+    _step_weight = LSTMLayer._step_weight
+
+    def setup(self, bottom, top):
+        p = self.param.recurrent_param
+        self.h = int(p.num_output)
+        self.expose = bool(p.expose_hidden)
+        # "resident" or "loop": the route of the last forward / backward
+        self.seq_route = None
+        self._wcast = {}
+        self._check_not_stateful()
+        n_in = len(bottom) - (1 if self.expose else 0)
+        if n_in not in (2, 3):
+            raise ValueError(
+                f"RNN layer {self.name!r}: {len(bottom)} bottoms with "
+                f"expose_hidden={self.expose}; expected x, cont, "
+                "[x_static][, h_0]")
+        if len(top) != (2 if self.expose else 1):
+            raise ValueError(
+                f"RNN layer {self.name!r}: tops are o"
+                + (", h_T with expose_hidden" if self.expose else ""))
+        self.static = n_in == 3
+        d = 1
+        for dim in bottom[0].shape[2:]:
+            d *= dim
+        H = self.h
+        self.add_param([H, d], p.weight_filler, name=self.name + "_Wxh")
+        self.add_param([H], p.bias_filler, name=self.name + "_bh")
+        if self.static:
+            ds = 1
+            for dim in bottom[2].shape[1:]:
+                ds *= dim
+            self.add_param([H, ds], p.weight_filler,
+                           name=self.name + "_Wxsh")
+        self.i_hh = len(self.blobs)
+        self.add_param([H, H], p.weight_filler, name=self.name + "_Whh")
+        self.add_param([H, H], p.weight_filler, name=self.name + "_Who")
+        self.add_param([H], p.bias_filler, name=self.name + "_bo")
+        self._cache = None
+
+    def _check_not_stateful(self):
+        if getattr(self.net, "recurrent_stateful", False):
+            raise RuntimeError(
+                f"RNN layer {self.name!r}: carrying state between forwards "
+                "(Net.set_recurrent_stateful) is implemented for LSTM "
+                "only; feed h_0 through recurrent_param.expose_hidden")
+
+    @staticmethod
+    def _native(t):
+        return t.is_cuda and t.dtype == torch.bfloat16
+
+    def forward(self, bottom, top):
+        self._check_not_stateful()
+        x = bottom[0].data
+        cont = bottom[1].data
+        T, N = x.shape[0], x.shape[1]
+        H, ih = self.h, self.i_hh
+        x2 = x.reshape(T * N, -1)
+        xg = ops.fc_forward(x2, self._step_weight(0), self._step_weight(1))
+        xg = xg.reshape(T, N, H)
+        if self.static:
+            xs = bottom[2].data.reshape(N, -1)
+            xg = xg + ops.fc_forward(xs, self._step_weight(2),
+                                     None).unsqueeze(0)
+        h0 = bottom[-1].data.reshape(N, H) if self.expose else None
+        ctx = {}
+        hs, seq_cache = ops.rnn_seq_forward(xg, self._step_weight(ih), cont,
+                                            h0, ctx)
+        self.seq_route = ctx["route"]
+        z = ops.fc_forward(hs.reshape(T * N, H), self._step_weight(ih + 1),
+                           self._step_weight(ih + 2))
+        # the output stage has a kernel of its own on the bf16 GPU path
+        o = ops.gpu_op("tanh_fwd")(z) if self._native(z) \
+            else ops.tanh_forward(z)
+        top[0].data = o.reshape(T, N, H)
+        if self.expose:
+            # a tensor of its own: hs stays intact for backward
+            top[1].data = hs[T - 1].reshape(1, N, H).clone()
+        self._cache = (x, hs, o, seq_cache)
+        return 0.0
+
+    def backward(self, top, propagate_down, bottom):
+        self._backward_grads(*self._backward_state(top), propagate_down,
+                             bottom)
+
+    def _backward_state(self, top):
+        """The serial half of backward: dz [T*N,H] at the output stage's
+        pre-activation with its GEMM's (dW_ho, db_o), dpre [T,N,H] at the
+        recurrence's pre-activation, dh0 or None."""
+        x, hs, o, seq_cache = self._cache
+        T, N = x.shape[0], x.shape[1]
+        H, ih = self.h, self.i_hh
+        do = top[0].diff.reshape(T * N, H).to(o.dtype)
+        dz = ops.gpu_op("tanh_bwd")(o, do) if self._native(o) \
+            else ops.tanh_backward(o, do)
+        dho, dw_ho, db_o = ops.fc_backward(
+            hs.reshape(T * N, H), self._step_weight(ih + 1), dz)
+        dh_T = top[1].diff if self.expose else None
+        ctx = {}
+        dpre, dh0 = ops.rnn_seq_backward(
+            dho.reshape(T, N, H), self._step_weight(ih), seq_cache,
+            None if dh_T is None else dh_T.reshape(N, H), ctx)
+        self.seq_route = ctx["route"]
+        return dz, (dw_ho, db_o), dpre, dh0
+
+    def _backward_grads(self, dz, out_grads, dpre, dh0, propagate_down,
+                        bottom):
+        """The GEMM half: the remaining gradients, all products of dpre."""
+        x, hs, o, seq_cache = self._cache
+        T, N = x.shape[0], x.shape[1]
+        H, ih = self.h, self.i_hh
+        dw_ho, db_o = out_grads
+        dpre2 = dpre.reshape(T * N, H)
+        # hc[t] = cont_t * h_{t-1}: pre_t = hc[t] W_hh^T + xg_t
+        hc2 = seq_cache[2].reshape(T * N, H)
+        _, dw_hh, _ = ops.fc_backward(hc2, self._step_weight(ih), dpre2,
+                                      need_dx=False, bias=False)
+        x2 = x.reshape(T * N, -1)
+        dx, dw_xh, db_h = ops.fc_backward(x2, self._step_weight(0), dpre2,
+                                          need_dx=propagate_down[0])
+        grads = {0: dw_xh, 1: db_h, ih: dw_hh, ih + 1: dw_ho, ih + 2: db_o}
+        if propagate_down[0]:
+            self.acc_blob_diff(bottom[0], dx.reshape(x.shape), False)
+        if self.static:
+            xs = bottom[2].data.reshape(N, -1)
+            d_static = dpre.float().sum(dim=0).to(dpre.dtype)   # [N, H]
+            dxs, grads[2], _ = ops.fc_backward(
+                xs, self._step_weight(2), d_static,
+                need_dx=propagate_down[2], bias=False)
+            if propagate_down[2]:
+                self.acc_blob_diff(bottom[2],
+                                   dxs.reshape(bottom[2].data.shape), False)
+        for i, g in grads.items():
+            if self.blobs[i]._lr_mult != 0:
+                self.acc_param_diff(i, g)
+        if self.expose and propagate_down[len(bottom) - 1]:
+            b = bottom[-1]
+            self.acc_blob_diff(
+                b, dh0.reshape(b.data.shape).to(b.data.dtype), False)
 
 
 @register_layer("Embed")

@@ -140,7 +140,7 @@ class Net:
                     p = False
                 if lp.type == "Embed" and i == 0:
                     p = False
-                if lp.type == "LSTM" and i == 1:
+                if lp.type in ("LSTM", "RNN") and i == 1:
                     p = False  # cont markers
                 prop.append(p)
             has_params = any(b._lr_mult != 0 for b in layer.blobs)

@@ -85,6 +85,7 @@ _FP32_REF_ON_GPU = {
     "embed_forward", "embed_backward", "lstm_unit_forward",
     "lstm_unit_backward", "bn_forward_train", "bn_forward_infer",
     "bn_backward", "accuracy", "bias_add",
+    "rnn_seq_forward", "rnn_seq_backward",
 }
 
 # fp32-route ops with a native fp32 HIP implementation, registered by
@@ -203,6 +204,8 @@ embed_forward = _dispatch("embed_forward")
 embed_backward = _dispatch("embed_backward")
 lstm_unit_forward = _dispatch("lstm_unit_forward")
 lstm_unit_backward = _dispatch("lstm_unit_backward")
+rnn_seq_forward = _dispatch("rnn_seq_forward")
+rnn_seq_backward = _dispatch("rnn_seq_backward")
 bn_forward_train = _dispatch("bn_forward_train")
 bn_forward_infer = _dispatch("bn_forward_infer")
 bn_backward = _dispatch("bn_backward")

@@ -211,6 +211,26 @@ void lstm_seq_bwd(const void* dy, const void* w_hcT, const void* cont,
                   void* dxg, void* dh_rec, float* dh_f, float* dc_a,
                   float* dc_b, int T, int N, int H, int n_alloc_whcT,
                   hipStream_t stream);
+bool rnn_seq_shape_ok(int64_t T, int64_t N, int64_t H);
+void rnn_seq_fwd(const void* xg, const void* w_hh, const float* cont,
+                 const void* h0, void* hs, void* hc, int T, int N, int H,
+                 hipStream_t stream);
+void rnn_seq_bwd(const void* dho, const void* w_hhT, const float* cont,
+                 const void* hs, const void* dhT, void* dpre, float* dh0,
+                 int T, int N, int H, hipStream_t stream);
+void rnn_step_fwd(const float* z, const void* xg_t, const float* cont_n,
+                  void* hs_t, void* hc_n, int64_t n, int H,
+                  hipStream_t stream);
+void rnn_step_bwd(const float* rec, const float* cont_n, const void* dho_t,
+                  const void* hs_t, const void* dhT, void* dpre_t, int64_t n,
+                  int H, hipStream_t stream);
+void rnn_scale0(const void* h0, void* hc0, float* rec, const float* cont0,
+                int64_t n, int H, hipStream_t stream);
+void tanh_fwd(const void* z, int64_t ldz, void* y, int64_t ldy, int64_t rows,
+              int cols, hipStream_t stream);
+void tanh_bwd(const void* y, int64_t ldy, const void* dy, int64_t lddy,
+              void* dz, int64_t lddz, int64_t rows, int cols,
+              hipStream_t stream);
 int64_t lstm_step_lds_bytes(int N, int D, int H, int Ds);
 void lstm_step(const void* x, const void* h_prev, const void* xs,
                const void* w_xc, const void* w_hc, const void* w_xsc,
@@ -1264,6 +1284,164 @@ void py_lstm_seq_bwd(Tensor dy, Tensor w_hcT, Tensor cont, Tensor h,
                        T, N, H, n_alloc, cur_stream());
 }
 
+// ---- RNN (csrc/rnn_seq.hip).  Every operand is checked against the extent
+// its kernel reads or writes.
+void rnn_bf(const Tensor& t, int64_t numel, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 &&
+              t.is_contiguous() && t.numel() == numel,
+              "rnn: ", what, " must be contiguous bf16 of ", numel,
+              " elements on the GPU");
+}
+void rnn_f32(const Tensor& t, int64_t numel, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat &&
+              t.is_contiguous() && t.numel() == numel,
+              "rnn: ", what, " must be contiguous fp32 of ", numel,
+              " elements on the GPU");
+}
+void rnn_al16(const Tensor& t, const char* what) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              "rnn: ", what, " must be 16-byte aligned");
+}
+
+bool py_rnn_seq_shape_ok(int64_t T, int64_t N, int64_t H) {
+  return cosamd::rnn_seq_shape_ok(T, N, H);
+}
+
+void py_rnn_seq_fwd(Tensor xg, Tensor w_hh, Tensor cont,
+                    c10::optional<Tensor> h0, Tensor hs, Tensor hc) {
+  TORCH_CHECK(xg.dim() == 3, "rnn_seq_fwd: xg is [T, N, H]");
+  int64_t T = xg.size(0), N = xg.size(1), H = xg.size(2);
+  TORCH_CHECK(cosamd::rnn_seq_shape_ok(T, N, H),
+              "rnn_seq_fwd: shape outside the resident kernel");
+  rnn_bf(xg, T * N * H, "xg"); rnn_bf(w_hh, H * H, "W_hh");
+  rnn_bf(hs, T * N * H, "hs"); rnn_bf(hc, T * N * H, "hc");
+  rnn_f32(cont, T * N, "cont");
+  rnn_al16(w_hh, "W_hh");
+  const void* h0p = nullptr;
+  if (h0.has_value()) {
+    rnn_bf(h0.value(), N * H, "h_0");
+    h0p = h0.value().data_ptr();
+  }
+  cosamd::rnn_seq_fwd(xg.data_ptr(), w_hh.data_ptr(),
+                      cont.data_ptr<float>(), h0p, hs.data_ptr(),
+                      hc.data_ptr(), (int)T, (int)N, (int)H, cur_stream());
+}
+
+void py_rnn_seq_bwd(Tensor dho, Tensor w_hhT, Tensor cont, Tensor hs,
+                    c10::optional<Tensor> dhT, Tensor dpre,
+                    c10::optional<Tensor> dh0) {
+  TORCH_CHECK(hs.dim() == 3, "rnn_seq_bwd: hs is [T, N, H]");
+  int64_t T = hs.size(0), N = hs.size(1), H = hs.size(2);
+  TORCH_CHECK(cosamd::rnn_seq_shape_ok(T, N, H),
+              "rnn_seq_bwd: shape outside the resident kernel");
+  rnn_bf(dho, T * N * H, "dho"); rnn_bf(w_hhT, H * H, "W_hh^T");
+  rnn_bf(hs, T * N * H, "hs"); rnn_bf(dpre, T * N * H, "dpre");
+  rnn_f32(cont, T * N, "cont");
+  rnn_al16(w_hhT, "W_hh^T");
+  const void* dhTp = nullptr;
+  float* dh0p = nullptr;
+  if (dhT.has_value()) {
+    rnn_bf(dhT.value(), N * H, "dh_T");
+    dhTp = dhT.value().data_ptr();
+  }
+  if (dh0.has_value()) {
+    rnn_f32(dh0.value(), N * H, "dh_0");
+    dh0p = dh0.value().data_ptr<float>();
+  }
+  cosamd::rnn_seq_bwd(dho.data_ptr(), w_hhT.data_ptr(),
+                      cont.data_ptr<float>(), hs.data_ptr(), dhTp,
+                      dpre.data_ptr(), dh0p, (int)T, (int)N, (int)H,
+                      cur_stream());
+}
+
+void py_rnn_step_fwd(Tensor z, Tensor xg_t, c10::optional<Tensor> cont_n,
+                     Tensor hs_t, c10::optional<Tensor> hc_n) {
+  TORCH_CHECK(z.dim() == 2, "rnn_step_fwd: z is [N, H]");
+  int64_t N = z.size(0), H = z.size(1);
+  TORCH_CHECK(cont_n.has_value() == hc_n.has_value(),
+              "rnn_step_fwd: cont and hc of the next step go together");
+  rnn_f32(z, N * H, "z"); rnn_bf(xg_t, N * H, "xg_t");
+  rnn_bf(hs_t, N * H, "hs_t");
+  const float* cp = nullptr;
+  void* hp = nullptr;
+  if (cont_n.has_value()) {
+    rnn_f32(cont_n.value(), N, "cont"); rnn_bf(hc_n.value(), N * H, "hc");
+    cp = cont_n.value().data_ptr<float>();
+    hp = hc_n.value().data_ptr();
+  }
+  cosamd::rnn_step_fwd(z.data_ptr<float>(), xg_t.data_ptr(), cp,
+                       hs_t.data_ptr(), hp, N * H, (int)H, cur_stream());
+}
+
+void py_rnn_step_bwd(c10::optional<Tensor> rec, c10::optional<Tensor> cont_n,
+                     Tensor dho_t, Tensor hs_t, c10::optional<Tensor> dhT,
+                     Tensor dpre_t) {
+  TORCH_CHECK(hs_t.dim() == 2, "rnn_step_bwd: hs_t is [N, H]");
+  int64_t N = hs_t.size(0), H = hs_t.size(1);
+  TORCH_CHECK(rec.has_value() == cont_n.has_value(),
+              "rnn_step_bwd: rec and cont of the next step go together");
+  rnn_bf(dho_t, N * H, "dho_t"); rnn_bf(hs_t, N * H, "hs_t");
+  rnn_bf(dpre_t, N * H, "dpre_t");
+  const float* rp = nullptr;
+  const float* cp = nullptr;
+  const void* tp = nullptr;
+  if (rec.has_value()) {
+    rnn_f32(rec.value(), N * H, "rec"); rnn_f32(cont_n.value(), N, "cont");
+    rp = rec.value().data_ptr<float>();
+    cp = cont_n.value().data_ptr<float>();
+  }
+  if (dhT.has_value()) {
+    rnn_bf(dhT.value(), N * H, "dh_T");
+    tp = dhT.value().data_ptr();
+  }
+  cosamd::rnn_step_bwd(rp, cp, dho_t.data_ptr(), hs_t.data_ptr(), tp,
+                       dpre_t.data_ptr(), N * H, (int)H, cur_stream());
+}
+
+// x bf16 with y given: y = cont0 * x (hc[0] from h_0); x fp32: x *= cont0
+void py_rnn_scale0(Tensor x, Tensor cont0, c10::optional<Tensor> y) {
+  TORCH_CHECK(x.dim() == 2, "rnn_scale0: x is [N, H]");
+  int64_t N = x.size(0), H = x.size(1);
+  rnn_f32(cont0, N, "cont_0");
+  if (y.has_value()) {
+    rnn_bf(x, N * H, "h_0"); rnn_bf(y.value(), N * H, "hc_0");
+    cosamd::rnn_scale0(x.data_ptr(), y.value().data_ptr(), nullptr,
+                       cont0.data_ptr<float>(), N * H, (int)H, cur_stream());
+  } else {
+    rnn_f32(x, N * H, "rec");
+    cosamd::rnn_scale0(nullptr, nullptr, x.data_ptr<float>(),
+                       cont0.data_ptr<float>(), N * H, (int)H, cur_stream());
+  }
+}
+
+// 2-D bf16 operands with unit column stride and a row stride of their own
+void rnn_rows(const Tensor& t, int64_t rows, int64_t cols, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 &&
+              t.dim() == 2 && t.size(0) == rows && t.size(1) == cols &&
+              (cols == 1 || t.stride(1) == 1) &&
+              (rows == 1 || t.stride(0) >= cols),
+              "tanh: ", what, " must be a ", rows, "x", cols,
+              " bf16 matrix with unit column stride on the GPU");
+}
+
+void py_tanh_fwd(Tensor z, Tensor y) {
+  TORCH_CHECK(z.dim() == 2, "tanh_fwd: 2-D operands");
+  int64_t rows = z.size(0), cols = z.size(1);
+  rnn_rows(z, rows, cols, "z"); rnn_rows(y, rows, cols, "y");
+  cosamd::tanh_fwd(z.data_ptr(), z.stride(0), y.data_ptr(), y.stride(0),
+                   rows, (int)cols, cur_stream());
+}
+
+void py_tanh_bwd(Tensor y, Tensor dy, Tensor dz) {
+  TORCH_CHECK(y.dim() == 2, "tanh_bwd: 2-D operands");
+  int64_t rows = y.size(0), cols = y.size(1);
+  rnn_rows(y, rows, cols, "y"); rnn_rows(dy, rows, cols, "dy");
+  rnn_rows(dz, rows, cols, "dz");
+  cosamd::tanh_bwd(y.data_ptr(), y.stride(0), dy.data_ptr(), dy.stride(0),
+                   dz.data_ptr(), dz.stride(0), rows, (int)cols,
+                   cur_stream());
+}
+
 void py_softmax_loss_fwd(Tensor x, Tensor label, Tensor prob,
                          Tensor rowloss, Tensor loss, Tensor count,
                          int64_t ignore, bool has_ignore) {
@@ -1405,6 +1583,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bias_act_cast", &py_bias_act_cast);
   m.def("lstm_seq_fwd", &py_lstm_seq_fwd);
   m.def("lstm_seq_bwd", &py_lstm_seq_bwd);
+  m.def("rnn_seq_shape_ok", &py_rnn_seq_shape_ok);
+  m.def("rnn_seq_fwd", &py_rnn_seq_fwd);
+  m.def("rnn_seq_bwd", &py_rnn_seq_bwd);
+  m.def("rnn_step_fwd", &py_rnn_step_fwd);
+  m.def("rnn_step_bwd", &py_rnn_step_bwd);
+  m.def("rnn_scale0", &py_rnn_scale0);
+  m.def("tanh_fwd", &py_tanh_fwd);
+  m.def("tanh_bwd", &py_tanh_bwd);
   m.def("lstm_unit_fwd", &py_lstm_unit_fwd);
   m.def("lstm_unit_bwd", &py_lstm_unit_bwd);
   m.def("lstm_step", &py_lstm_step);

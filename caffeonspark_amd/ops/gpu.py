@@ -2228,6 +2228,144 @@ def lstm_seq_backward(dy, w_hc, cache, ctx=None):
     return dxg, dwhc
 
 
+# -------------------------------------------------------------------- RNN
+#
+# Plain tanh recurrence (csrc/rnn_seq.hip).  Route "resident": one launch
+# per direction, a workgroup keeps 16 batch rows' state in LDS for all T
+# steps.  Route "loop": per step one GEMM into fp32 plus the step kernel.
+# The resident route's step time grows with H^2 (16 output slabs of H/32
+# K chunks per wave at H = 1024) while the loop's stays near its launch
+# cost, so by default the resident kernels serve H <= 256, where they
+# measured faster ("RNN").  COS_RNN_SEQ=0 sends every shape to
+# the loop, COS_RNN_SEQ=1 every shape the kernels can run to them; it is
+# read on every call.
+_RNN_SEQ_MAXH_DEFAULT = 256
+
+
+def _rnn_seq_ok(N, H, tensors):
+    """True when the resident kernels serve this shape: bf16 operands they
+    can read in place (contiguous, 16-byte aligned), H a multiple of 32 and
+    at most 2048 (two 16 x (H + 8) bf16 state tiles within the 160 KB of
+    LDS), and H inside the measured-faster region unless COS_RNN_SEQ=1."""
+    flag = os.environ.get("COS_RNN_SEQ")
+    if flag == "0" or (flag != "1" and H > _RNN_SEQ_MAXH_DEFAULT):
+        return False
+    if not _ext.rnn_seq_shape_ok(1, N, H):
+        return False
+    return all(t.dtype == torch.bfloat16 and t.is_contiguous()
+               and t.data_ptr() % 16 == 0 for t in tensors)
+
+
+def _rnn_rows(numel_rows, H, device):
+    """[rows, H] bf16 with 128 readable rows beyond the end, so that a
+    per-step slice of it keeps the GEMM's fast A staging."""
+    store = torch.empty(((numel_rows + 128) * H,), dtype=torch.bfloat16,
+                        device=device)
+    return store[:numel_rows * H]
+
+
+def rnn_seq_forward(xg, w_hh, cont, h0=None, ctx=None):
+    """Whole-sequence tanh recurrence h_t = tanh(W_hh (cont_t h_{t-1}) +
+    xg_t).  xg: [T,N,H] input projection with bias, w_hh: [H,H], cont:
+    [T,N], h0: [N,H] or None for a zero start.  Returns (hs [T,N,H] bf16,
+    cache); ctx, when given, gets ctx["route"]: "resident" or "loop"."""
+    T, N, H = xg.shape
+    dev_ = xg.device
+    xg = _as_bf16(xg).contiguous()
+    whh = _as_bf16(w_hh).contiguous()
+    cont_f = cont.reshape(T, N).float().contiguous()
+    h0b = None if h0 is None else _as_bf16(h0).reshape(N, H).contiguous()
+    hs = torch.empty((T, N, H), dtype=torch.bfloat16, device=dev_)
+    # hc[t] = cont_t * h_{t-1}: the W_hh gradient GEMM's operand
+    hc = _rnn_rows(T * N, H, dev_).view(T, N, H)
+    if _rnn_seq_ok(N, H, [xg, whh] + ([] if h0b is None else [h0b])):
+        route = "resident"
+        _ext.rnn_seq_fwd(xg, whh, cont_f, h0b, hs, hc)
+    else:
+        route = "loop"
+        if h0b is None:
+            hc[0].zero_()
+        else:
+            _ext.rnn_scale0(h0b, cont_f[0], hc[0])
+        z = torch.empty((N, H), dtype=torch.float32, device=dev_)
+        for t in range(T):
+            more = t + 1 < T
+            _gemm(hc[t], whh, z, None, N, H, H, H, H, H, False, False, 1, 1,
+                  ma=N + 128, na=H)
+            _ext.rnn_step_fwd(z, xg[t], cont_f[t + 1] if more else None,
+                              hs[t], hc[t + 1] if more else None)
+    if ctx is not None:
+        ctx["route"] = route
+    return hs, (cont_f, hs, hc, h0b is not None)
+
+
+def rnn_seq_backward(dho, w_hh, cache, dh_T=None, ctx=None):
+    """dho: [T,N,H] gradient reaching every h_t from the output stage,
+    dh_T: [N,H] gradient of an exposed final state or None.  Returns
+    (dpre [T,N,H] bf16, dh0 [N,H] fp32 or None): the gradient at the
+    pre-activation of every step, and of h_0 when forward was given one."""
+    cont_f, hs, hc, has_h0 = cache
+    T, N, H = hs.shape
+    dev_ = hs.device
+    dho = _as_bf16(dho).reshape(T, N, H).contiguous()
+    whhT = _transpose(_as_bf16(w_hh).contiguous())     # [in][out]
+    dhT = None if dh_T is None \
+        else _as_bf16(dh_T).reshape(N, H).contiguous()
+    dpre = _rnn_rows(T * N, H, dev_).view(T, N, H)
+    dh0 = None
+    if _rnn_seq_ok(N, H, [dho, whhT] + ([] if dhT is None else [dhT])):
+        route = "resident"
+        if has_h0:
+            dh0 = torch.empty((N, H), dtype=torch.float32, device=dev_)
+        _ext.rnn_seq_bwd(dho, whhT, cont_f, hs, dhT, dpre, dh0)
+    else:
+        route = "loop"
+        rec = torch.empty((N, H), dtype=torch.float32, device=dev_)
+
+        def rec_from(dpre_t):       # rec = dpre_t @ W_hh
+            _gemm(dpre_t, whhT, rec, None, N, H, H, H, H, H, False, False,
+                  1, 1, ma=N + 128, na=_pad128(H))
+
+        for t in reversed(range(T)):
+            last = t == T - 1
+            if not last:
+                rec_from(dpre[t + 1])
+            _ext.rnn_step_bwd(None if last else rec,
+                              None if last else cont_f[t + 1], dho[t], hs[t],
+                              dhT if last else None, dpre[t])
+        if has_h0:
+            rec_from(dpre[0])
+            _ext.rnn_scale0(rec, cont_f[0], None)
+            dh0 = rec
+    if ctx is not None:
+        ctx["route"] = route
+    return dpre, dh0
+
+
+def _rows2d(t):
+    """t as a 2-D matrix with unit column stride (the last dim kept)."""
+    t2 = t.reshape(-1, t.shape[-1])
+    return t2 if t2.stride(1) == 1 or t2.shape[1] == 1 else t2.contiguous()
+
+
+def tanh_fwd(z):
+    """y = tanh(z) on the HIP kernel (bf16; rows may be strided)."""
+    _check_bf16(z, "tanh input")
+    z2 = _rows2d(z)
+    y = torch.empty(z2.shape, dtype=torch.bfloat16, device=z.device)
+    _ext.tanh_fwd(z2, y)
+    return y.view(z.shape)
+
+
+def tanh_bwd(y, dy):
+    """dz = dy * (1 - y^2) on the HIP kernel."""
+    _check_bf16(y, "tanh output")
+    y2, dy2 = _rows2d(y), _rows2d(_as_bf16(dy))
+    dz = torch.empty(y2.shape, dtype=torch.bfloat16, device=y.device)
+    _ext.tanh_bwd(y2, dy2, dz)
+    return dz.view(y.shape)
+
+
 # -------------------------------------------------------------- batchnorm
 
 def _bn_eligible(x):

@@ -337,6 +337,50 @@ def lstm_unit_backward(c_prev, cache, dc_next, dh):
     return dc_prev, d_gates.reshape(n, -1)
 
 
+# ------------------------------------------------------------------------ RNN
+
+def rnn_seq_forward(xg, w_hh, cont, h0=None, ctx=None):
+    """h_t = tanh(W_hh (cont_t h_{t-1}) + xg_t) over a whole sequence.
+    xg: [T, N, H] input projection with bias, w_hh: [H, H], cont: [T, N],
+    h0: [N, H] or None (zero start).  Returns (hs [T, N, H], cache); the
+    cache is (cont [T, N], hs, hc, h0 given), hc[t] = cont_t h_{t-1}."""
+    T, N, H = xg.shape
+    c = cont.reshape(T, N).to(xg.dtype)
+    w = w_hh.to(xg.dtype)
+    h = torch.zeros(N, H, dtype=xg.dtype, device=xg.device) if h0 is None \
+        else h0.reshape(N, H).to(xg.dtype)
+    hs, hc = [], []
+    for t in range(T):
+        h_in = h * c[t].unsqueeze(1)
+        h = torch.tanh(xg[t] + h_in @ w.t())
+        hc.append(h_in)
+        hs.append(h)
+    if ctx is not None:
+        ctx["route"] = "loop"
+    hs = torch.stack(hs, dim=0)
+    return hs, (c, hs, torch.stack(hc, dim=0), h0 is not None)
+
+
+def rnn_seq_backward(dho, w_hh, cache, dh_T=None, ctx=None):
+    """dho: [T, N, H] gradient reaching each h_t from above, dh_T: [N, H]
+    gradient of the final state or None.  Returns (dpre [T, N, H], dh0
+    [N, H] or None): dpre_t = dh_t (1 - h_t^2) with dh_t = dho_t +
+    cont_{t+1} (dpre_{t+1} W_hh)."""
+    c, hs, _, has_h0 = cache
+    T, N, H = hs.shape
+    w = w_hh.to(hs.dtype)
+    dho = dho.reshape(T, N, H).to(hs.dtype)
+    carry = torch.zeros_like(hs[0]) if dh_T is None \
+        else dh_T.reshape(N, H).to(hs.dtype)
+    dpre = [None] * T
+    for t in reversed(range(T)):
+        dpre[t] = (dho[t] + carry) * (1.0 - hs[t] * hs[t])
+        carry = (dpre[t] @ w) * c[t].unsqueeze(1)
+    if ctx is not None:
+        ctx["route"] = "loop"
+    return torch.stack(dpre, dim=0), (carry if has_h0 else None)
+
+
 # -------------------------------------------------------------------- concat &c
 
 def accuracy(x, label, top_k=1, ignore_label: Optional[int] = None,

@@ -41,9 +41,11 @@ void gemm_conv_fwd(const void* X, const void* B, void* C,
                    const float* bias, const void* zpage, int M, int N,
                    int K, int ldb, int ldc, bool relu, bool accum,
                    const int* geom, int groups, int gs_c, int gs_b,
-                   int gs_n, int cfg, int vec, hipStream_t stream);
+                   int gs_n, int cfg, int vec, int incr,
+                   hipStream_t stream);
 struct ConvCfg { int id, bm, bn, waves, depth; };
 ConvCfg conv_fwd_plan(int M, int N, int K);
+bool conv_fwd_incr(int M, const int* geom, int incr);
 int conv_fwd_num_cfgs();
 ConvCfg conv_fwd_cfg(int id);
 void gemm_conv_dw(const void* A, const void* X, float* C,
@@ -455,7 +457,7 @@ void py_gemm_conv_fwd(Tensor X, Tensor B, Tensor C,
                       int64_t ldc, bool relu, bool accum,
                       std::vector<int64_t> geom, int64_t groups,
                       int64_t gs_c, int64_t gs_b, int64_t gs_n,
-                      int64_t cfg, int64_t vec) {
+                      int64_t cfg, int64_t vec, int64_t incr) {
   CHECK_CUDA(X); CHECK_BF16(X); CHECK_BF16(B); CHECK_BF16(C);
   TORCH_CHECK(groups >= 1, "groups must be positive");
   const float* bptr = nullptr;
@@ -470,13 +472,24 @@ void py_gemm_conv_fwd(Tensor X, Tensor B, Tensor C,
                         zpage.data_ptr(), (int)M, (int)N, (int)K,
                         (int)ldb, (int)ldc, relu, accum, g, (int)groups,
                         (int)gs_c, (int)gs_b, (int)gs_n, (int)cfg, (int)vec,
-                        cur_stream());
+                        (int)incr, cur_stream());
 }
 
-// (BM, BN, waves, ring depth) gemm_conv_fwd picks for [M, N, K]
-std::vector<int64_t> py_conv_fwd_plan(int64_t M, int64_t N, int64_t K) {
+// (BM, BN, waves, ring depth) gemm_conv_fwd picks for [M, N, K]; given the
+// launch's geom (and its incr argument) a fifth number says which A
+// staging it takes: 1 walked addresses, 0 divided per tile
+std::vector<int64_t> py_conv_fwd_plan(int64_t M, int64_t N, int64_t K,
+                                      std::vector<int64_t> geom,
+                                      int64_t incr) {
   cosamd::ConvCfg p = cosamd::conv_fwd_plan((int)M, (int)N, (int)K);
-  return {p.bm, p.bn, p.waves, p.depth};
+  std::vector<int64_t> out = {p.bm, p.bn, p.waves, p.depth};
+  if (!geom.empty()) {
+    int g[14];
+    TORCH_CHECK(geom.size() == 14, "geom must have 14 ints");
+    for (int i = 0; i < 14; ++i) g[i] = (int)geom[i];
+    out.push_back(cosamd::conv_fwd_incr((int)M, g, (int)incr) ? 1 : 0);
+  }
+  return out;
 }
 
 // the same four numbers for every configuration id (the cfg argument)
@@ -1482,8 +1495,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("N"), py::arg("K"), py::arg("ldb"), py::arg("ldc"),
         py::arg("relu"), py::arg("accum"), py::arg("geom"),
         py::arg("groups") = 1, py::arg("gs_c") = 0, py::arg("gs_b") = 0,
-        py::arg("gs_n") = 0, py::arg("cfg") = -1, py::arg("vec") = -1);
-  m.def("conv_fwd_plan", &py_conv_fwd_plan);
+        py::arg("gs_n") = 0, py::arg("cfg") = -1, py::arg("vec") = -1,
+        py::arg("incr") = -1);
+  m.def("conv_fwd_plan", &py_conv_fwd_plan, py::arg("M"), py::arg("N"),
+        py::arg("K"), py::arg("geom") = std::vector<int64_t>{},
+        py::arg("incr") = -1);
   m.def("conv_fwd_cfgs", &py_conv_fwd_cfgs);
   m.def("gemm_conv_dw", &py_gemm_conv_dw);
   m.def("gemm_conv_fwd_sc", &py_gemm_conv_fwd_sc);

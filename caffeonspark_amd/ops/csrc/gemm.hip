@@ -29,8 +29,14 @@
 //     with ADirect (direct-to-LDS DMA), everything else a guarded loop.
 //     All 16 TAxTBxSTORE_MODE combinations at WAVES=4, NN also at WAVES=8.
 //   gemm_conv_fwd_kernel<TileCfg, DEPTH>         gemm_conv_fwd
-//     pipelined_loop with AImplicit (im2col gather DMA) on a block tile
-//     chosen per launch by conv_fwd_plan (COS_CONV_CFGS lists every
+//     pipelined_loop with the im2col gather DMA as its A stage, on a block
+//     tile chosen per launch by conv_fwd_plan.  The gather's address is
+//     walked from K tile to K tile in registers (AImplicitIncr: no
+//     division, multiply or LDS read in the loop) when Cg >= 32 and the
+//     input's byte offsets fit 32 bits, and re-derived per tile by magic
+//     division (AImplicit) otherwise; incr=0 / COS_CONV_INCR=0 force the
+//     latter, conv_fwd_incr reports the choice, results are bit-identical.
+//     Tile selection, by conv_fwd_plan (COS_CONV_CFGS lists every
 //     instantiation).  N tile: the one of 48/64/96/128 columns with the
 //     least padding, the wider on a tie; COS_CONV_BN=48/64/96/128 forces
 //     one (0/unset: automatic); unlike COS_CONVQ it is read on every
@@ -497,6 +503,7 @@ struct CGeom {
   int sh, sw, ph, pw, dil, S;
   int c0, Cg;                        // group channel window
   int Kcol;                          // R*S*Cg (zero beyond)
+  int R;                             // Kcol / (S*Cg): AImplicitIncr's k bound
   // magic reciprocals: floor(n/d) == (n * m) >> 40 for n < 2^20
   unsigned long long mPQ, mQ, mCg, mS;
 };
@@ -863,6 +870,101 @@ struct AImplicit {        // im2col gather from the NHWC input
   }
 };
 
+// The same gather as AImplicit — same bytes to the same LDS positions —
+// with the address walked instead of re-derived per tile.  Three facts
+// make the state small:
+//   - the swizzled k offset of a lane, kk, depends on the lane alone
+//     ((row >> 1) & 3 == (lane >> 3) & 3 for every 16-row chunk), so all
+//     CPW chunks of a wave share one (r, s, c);
+//   - pipelined_loop stages tiles k_begin, k_begin + BK, ... each exactly
+//     once and in order, so (r, s, c) advances by BK per stage() call: one
+//     add and, with Cg >= BK, at most one carry into s and one into r;
+//   - a row's (n*H*W, p*sh - ph, q*sw - pw) never changes in the K loop.
+// Held per chunk: h0, w0 and the byte offset of the row's current tap,
+// ((nHW + (h0 + r*dil)*W + w0 + s*dil)*C + c0 + c) * 2; per lane: c,
+// r*dil and s*dil.  k itself is not kept: Kcol = R*S*Cg, so k < Kcol is
+// r < R.
+// Offsets are 32-bit and unsigned (a row that starts in the padding has a
+// "negative" base that the tap brings back, modulo 2^32), so the host
+// takes this form only when X's addressed bytes stay below 2^32
+// (conv_incr_ok); the k0 argument of stage() is implied by the call count
+// and ignored.  The DMA issues unconditionally as in stage_implicit_fast.
+template <int CPW>
+struct AImplicitIncr {
+  const bf16* X;
+  const bf16* zpage;
+  const CGeom& gm;
+  unsigned h0[CPW], w0[CPW], off[CPW];
+  unsigned c, rdil, sdil;
+  int wave;                 // through an SGPR: M0 by scalar instructions
+
+  // k_begin: the first tile staged; rinfo must be complete (barrier)
+  __device__ __forceinline__ AImplicitIncr(
+      const bf16* X_, const bf16* zpage_, const CGeom& gm_, const int* rinfo,
+      int k_begin, int tid) : X(X_), zpage(zpage_), gm(gm_) {
+    wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int lane = tid & 63;
+    unsigned k = k_begin + (swz_chunk(lane >> 2, lane & 3) << 3);
+    unsigned rs = mdiv(k, gm.mCg);
+    c = k - rs * gm.Cg;
+    unsigned r = mdiv(rs, gm.mS);
+    rdil = r * gm.dil;
+    sdil = (rs - r * gm.S) * gm.dil;
+    unsigned tap = (rdil * (unsigned)gm.W + sdil) * (unsigned)gm.C + c;
+#pragma unroll
+    for (int it = 0; it < CPW; ++it) {
+      int row = (wave * CPW + it) * 16 + (lane >> 2);
+      h0[it] = (unsigned)rinfo[row * 3 + 1];
+      w0[it] = (unsigned)rinfo[row * 3 + 2];
+      off[it] = (((unsigned)rinfo[row * 3] + h0[it] * (unsigned)gm.W +
+                  w0[it]) * (unsigned)gm.C + (unsigned)gm.c0 + tap) * 2u;
+    }
+  }
+
+  template <int WAVES, int CHUNKS>
+  __device__ __forceinline__ void stage(bf16* lds_, int, int) {
+    static_assert(CHUNKS / WAVES == CPW, "state sized for this tile");
+    auto* lds = reinterpret_cast<unsigned short*>(lds_);
+    bool k_ok = rdil < (unsigned)(gm.R * gm.dil);
+#pragma unroll
+    for (int it = 0; it < CPW; ++it) {
+      // unsigned compares fold the >= 0 tests; & not &&: no branches
+      bool ok = k_ok & (h0[it] + rdil < (unsigned)gm.H) &
+                (w0[it] + sdil < (unsigned)gm.W);
+      const char* src = ok ? reinterpret_cast<const char*>(X) + off[it]
+                           : reinterpret_cast<const char*>(zpage);
+      auto* lp = (__attribute__((address_space(3))) unsigned int*)(
+          lds + (wave * CPW + it) * 512);
+      auto* gp = (const __attribute__((address_space(1))) unsigned int*)src;
+      __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
+    }
+    // advance by one K tile; Cg >= BK: one carry out of c at the most,
+    // and s reaches S only through that carry.  The carries are masks
+    // and'ed with the uniform steps, not selects: a select's condition
+    // takes the one scalar operand an instruction may have, so every
+    // uniform step would sit in a VGPR of its own for the whole loop
+    // (opaque() keeps the compiler from turning them back into selects).
+    auto opaque = [](unsigned m) {
+      asm volatile("" : "+v"(m));
+      return m;
+    };
+    unsigned sC = (unsigned)(gm.dil * gm.C - gm.Cg) * 2u;
+    unsigned rC = (unsigned)((gm.W - gm.S) * gm.dil * gm.C) * 2u;
+    c += BK;
+    bool cs = c >= (unsigned)gm.Cg;
+    c -= cs ? (unsigned)gm.Cg : 0u;
+    unsigned ms = opaque(cs ? ~0u : 0u);
+    sdil += ms & (unsigned)gm.dil;
+    bool cr = sdil == (unsigned)(gm.S * gm.dil);
+    sdil = cr ? 0u : sdil;
+    unsigned mr = opaque(cr ? ~0u : 0u);
+    rdil += mr & (unsigned)gm.dil;
+    unsigned step = BK * 2 + (ms & sC) + (mr & rC);
+#pragma unroll
+    for (int it = 0; it < CPW; ++it) off[it] += step;
+  }
+};
+
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -870,9 +972,11 @@ __device__ __forceinline__ void wait_vmcnt() {
 
 // Asb / Bsb: the ring's DEPTH stages of Cfg::A_ELEMS / Cfg::B_ELEMS each.
 // zpage / b_rows: stage_direct_fast's guard for B (nullptr: none).
+// astage.stage() is called once per staged tile, in ascending k order, at
+// either depth (the prologue's tiles first): AImplicitIncr counts on it.
 template <class Cfg, int DEPTH, class AStage>
 __device__ __forceinline__ void pipelined_loop(
-    bf16* Asb, bf16* Bsb, const AStage& astage, const bf16* B,
+    bf16* Asb, bf16* Bsb, AStage&& astage, const bf16* B,
     const bf16* zpage, int b_rows, int tile_n, int ldb, int k_begin,
     int k_end, int tid, int wm, int wn, int lane,
     f32x4 (&acc)[Cfg::MF][Cfg::NF]) {
@@ -1024,8 +1128,32 @@ __global__ __launch_bounds__(WAVES * 64, 2) void gemm_kernel(
 //
 // One __shared__ object for ring and rinfo: a second object beside a
 // DMA-staged array can make the compiler drain vmcnt before LDS reads.
-template <class Cfg, int DEPTH>
-__global__ __launch_bounds__(Cfg::WAVES * 64, 2) void gemm_conv_fwd_kernel(
+//
+// INCR: AImplicitIncr (walked addresses) instead of AImplicit (divided per
+// tile); the host picks it, see conv_incr_ok.  Same results bit for bit.
+//
+// Its state costs registers, and three tiles sit right at the VGPR count
+// their blocks per CU allow (profiles/alexnet_1gpu_conv_tiles.md), so the
+// INCR kernels name that occupancy and the register allocator holds it;
+// the others keep the two blocks per CU of the launch bound.
+template <class Cfg, int DEPTH, bool INCR>
+constexpr int conv_waves_per_simd() {
+  if (!INCR) return 2 * Cfg::WAVES / 4;
+  constexpr int ring = DEPTH * (Cfg::A_ELEMS + Cfg::B_ELEMS) * 2 +
+                       Cfg::TBM * 12;
+  int blocks = 160 * 1024 / ring;            // what the LDS allows
+  int waves = blocks * Cfg::WAVES / 4;
+  // 32 accumulator + 24 fragment registers: 128x128 8w stops at 6 waves,
+  // 128x128 4w (64 + 32) at 4
+  int cap = Cfg::TBN == 128 ? (Cfg::WAVES == 8 ? 6 : 4) : 8;
+  return waves < cap ? waves : cap;
+}
+
+template <class Cfg, int DEPTH, bool INCR>
+__global__ __attribute__((
+    amdgpu_flat_work_group_size(Cfg::WAVES * 64, Cfg::WAVES * 64),
+    amdgpu_waves_per_eu(conv_waves_per_simd<Cfg, DEPTH, INCR>())))
+void gemm_conv_fwd_kernel(
     const bf16* __restrict__ X, const bf16* __restrict__ B,
     bf16* __restrict__ C, const float* __restrict__ bias,
     const bf16* __restrict__ zpage,
@@ -1059,9 +1187,15 @@ __global__ __launch_bounds__(Cfg::WAVES * 64, 2) void gemm_conv_fwd_kernel(
   __syncthreads();
 
   f32x4 acc[Cfg::MF][Cfg::NF] = {};
-  pipelined_loop<Cfg, DEPTH>(Asb, Bsb, AImplicit{X, zpage, gm, rinfo}, B,
-                             zpage, b_rows, t.tile_n, ldb, 0, K, tid, wm,
-                             wn, lane, acc);
+  if constexpr (INCR) {
+    AImplicitIncr<Cfg::A_CPW> astage(X, zpage, gm, rinfo, 0, tid);
+    pipelined_loop<Cfg, DEPTH>(Asb, Bsb, astage, B, zpage, b_rows, t.tile_n,
+                               ldb, 0, K, tid, wm, wn, lane, acc);
+  } else {
+    pipelined_loop<Cfg, DEPTH>(Asb, Bsb, AImplicit{X, zpage, gm, rinfo}, B,
+                               zpage, b_rows, t.tile_n, ldb, 0, K, tid, wm,
+                               wn, lane, acc);
+  }
   if (vec) {
     __syncthreads();                 // every wave is done reading the ring
     epilogue_bf16_vec<Cfg>(acc, reinterpret_cast<float*>(smem), C, bias, M,
@@ -1505,6 +1639,7 @@ static CGeom make_geom(const int* g) {
   gm.sh = g[5]; gm.sw = g[6]; gm.ph = g[7]; gm.pw = g[8];
   gm.dil = g[9]; gm.S = g[10];
   gm.c0 = g[11]; gm.Cg = g[12]; gm.Kcol = g[13];
+  gm.R = gm.Kcol / (gm.S * gm.Cg);
   gm.mPQ = magic40(gm.PQ);
   gm.mQ = magic40(gm.Q);
   gm.mCg = magic40(gm.Cg);
@@ -1612,15 +1747,41 @@ ConvCfg conv_fwd_plan(int M, int N, int K) {
   return kConvCfgs[id];
 }
 
+// Which A staging a launch takes: the walked one (AImplicitIncr) needs a
+// carry of at most one tap per K tile (Cg >= BK) and 32-bit byte offsets
+// (the images the M rows reach, all C channels of them, below 4 GiB), and
+// tests k < Kcol as r < R, so Kcol must be whole taps; anything else keeps
+// the divide form.  incr: 0 forces the divide form,
+// 1 takes the walked one wherever the kernel supports it, -1 is automatic:
+// as 1 unless COS_CONV_INCR=0 (read per call, like COS_CONV_BN).  No
+// AlexNet shape measured slower with it (profiles/
+// alexnet_1gpu_conv_incr.md), so the automatic choice gates nothing else.
+static bool conv_incr_ok(const CGeom& gm, int M, int incr) {
+  if (incr == 0) return false;
+  if (incr < 0) {
+    const char* e = getenv("COS_CONV_INCR");
+    if (e && e[0] == '0') return false;
+  }
+  int64_t images = ((int64_t)M + gm.PQ - 1) / gm.PQ;
+  int64_t bytes = images * gm.H * gm.W * gm.C * (int64_t)sizeof(bf16);
+  return gm.Cg >= BK && gm.Kcol == gm.R * gm.S * gm.Cg &&
+         bytes < (1ll << 32);
+}
+
+bool conv_fwd_incr(int M, const int* geom, int incr) {
+  return conv_incr_ok(make_geom(geom), M, incr);
+}
+
 // groups > 1 runs a grouped convolution in one launch; see the kernel
 // for the three strides.  cfg >= 0 forces an instantiation (the sweep).
 // vec: 0 element-wise epilogue, 1 the 16-byte one where the operands
-// allow it, -1 automatic (conv_vec).
+// allow it, -1 automatic (conv_vec).  incr: see conv_incr_ok.
 void gemm_conv_fwd(const void* X, const void* B, void* C,
                    const float* bias, const void* zpage, int M, int N,
                    int K, int ldb, int ldc, bool relu, bool accum,
                    const int* geom, int groups, int gs_c, int gs_b,
-                   int gs_n, int cfg, int vec, hipStream_t stream) {
+                   int gs_n, int cfg, int vec, int incr,
+                   hipStream_t stream) {
   CGeom gm = make_geom(geom);
   if (K % BK != 0 || K < 2 * BK)
     throw std::runtime_error("gemm_conv_fwd: K must be whole 32-wide tiles, "
@@ -1634,18 +1795,23 @@ void gemm_conv_fwd(const void* X, const void* B, void* C,
   bool vec_ok = ((N | ldc | (groups > 1 ? gs_n : 0)) % 8 == 0) &&
                 (((uintptr_t)C | (uintptr_t)bias) % 16 == 0);
   int use_vec = vec_ok && (vec < 0 ? conv_vec(p.id) : vec != 0);
+  bool use_incr = conv_incr_ok(gm, M, incr);
+#define LAUNCH_(TBM, TBN, WM, WN, DEPTH, INCR)                              \
+  gemm_conv_fwd_kernel<TileCfg<TBM, TBN, WM, WN>, DEPTH, INCR>              \
+      <<<grid, WM * WN * 64, 0, stream>>>(                                  \
+          (const bf16*)X, (const bf16*)B, (bf16*)C, bias,                   \
+          (const bf16*)zpage, M, N, K, ldb, ldc, relu ? 1 : 0,              \
+          accum ? 1 : 0, gm, gs_c, gs_b, gs_n, use_vec)
   switch (p.id) {
 #define CFG_(ID, TBM, TBN, WM, WN, DEPTH)                                   \
     case ID:                                                                \
-      gemm_conv_fwd_kernel<TileCfg<TBM, TBN, WM, WN>, DEPTH>                \
-          <<<grid, WM * WN * 64, 0, stream>>>(                              \
-              (const bf16*)X, (const bf16*)B, (bf16*)C, bias,               \
-              (const bf16*)zpage, M, N, K, ldb, ldc, relu ? 1 : 0,          \
-              accum ? 1 : 0, gm, gs_c, gs_b, gs_n, use_vec);                \
+      if (use_incr) LAUNCH_(TBM, TBN, WM, WN, DEPTH, true);                 \
+      else LAUNCH_(TBM, TBN, WM, WN, DEPTH, false);                         \
       break;
     COS_CONV_CFGS(CFG_)
 #undef CFG_
   }
+#undef LAUNCH_
 }
 
 void gemm_conv_fwd_sc(const void* X, const void* B, void* C,

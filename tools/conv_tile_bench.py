@@ -14,9 +14,10 @@ has no conv_fwd_plan).
   python tools/conv_tile_bench.py --grouped       # all groups, one launch
   python tools/conv_tile_bench.py --sweep         # every configuration id
   python tools/conv_tile_bench.py --sweep --vec 0 # ... element-wise epilogue
+  python tools/conv_tile_bench.py --grouped --incr 0  # divide-form A staging
   COS_CONV_BN=128 python tools/conv_tile_bench.py # the fixed 128-wide tile
 
-Without --grouped, --sweep and --vec it uses only the 13-argument binding, so it
+Without --grouped, --sweep, --vec and --incr it uses only the 13-argument binding, so it
 runs unchanged on a build from before the tile selection.
 """
 
@@ -103,11 +104,13 @@ def _buffers(row, dev):
     return sets
 
 
-def _time(ext, row, sets, zpage, grouped, cfg, vec):
+def _time(ext, row, sets, zpage, grouped, cfg, vec, incr):
     gs_c, gs_b, gs_n = row["gs"]
     extra = ()
-    if grouped or cfg >= 0 or vec >= 0:
+    if grouped or cfg >= 0 or vec >= 0 or incr >= 0:
         extra = (row["groups"] if grouped else 1, gs_c, gs_b, gs_n, cfg, vec)
+        if incr >= 0:
+            extra += (incr,)
     us = []
     for i in range(WARMUP + LAUNCHES):
         x, w, y = sets[i % len(sets)]
@@ -134,6 +137,9 @@ def main():
     ap.add_argument("--vec", type=int, default=-1,
                     help="epilogue: 0 element-wise, 1 16-byte stores, "
                          "-1 the build's choice")
+    ap.add_argument("--incr", type=int, default=-1,
+                    help="A staging: 0 divided per tile, 1 walked, "
+                         "-1 the build's choice")
     ap.add_argument("--out", help="also write the rows as JSON here")
     args = ap.parse_args()
 
@@ -153,7 +159,7 @@ def main():
         table = ext.conv_fwd_cfgs() if args.sweep else None
         for cfg in (range(len(table)) if args.sweep else [-1]):
             med, lo, hi = _time(ext, row, sets, zpage, args.grouped, cfg,
-                                args.vec)
+                                args.vec, args.incr)
             launches = 1 if args.grouped else row["groups"]
             gmul = row["groups"] if args.grouped else 1
             bn, shape = 128, "128x128"

@@ -44,7 +44,7 @@ void gemm_conv_fwd(const void* X, const void* B, void* C,
                    int gs_n, int cfg, int vec, int incr,
                    hipStream_t stream);
 struct ConvCfg { int id, bm, bn, waves, depth; };
-ConvCfg conv_fwd_plan(int M, int N, int K);
+ConvCfg conv_fwd_plan(int M, int N, int K, int groups);
 bool conv_fwd_incr(int M, const int* geom, int incr);
 int conv_fwd_num_cfgs();
 ConvCfg conv_fwd_cfg(int id);
@@ -477,11 +477,13 @@ void py_gemm_conv_fwd(Tensor X, Tensor B, Tensor C,
 
 // (BM, BN, waves, ring depth) gemm_conv_fwd picks for [M, N, K]; given the
 // launch's geom (and its incr argument) a fifth number says which A
-// staging it takes: 1 walked addresses, 0 divided per tile
+// staging it takes: 1 walked addresses, 0 divided per tile.  N is per
+// group; groups is the launch's group count (the plan counts its blocks)
 std::vector<int64_t> py_conv_fwd_plan(int64_t M, int64_t N, int64_t K,
                                       std::vector<int64_t> geom,
-                                      int64_t incr) {
-  cosamd::ConvCfg p = cosamd::conv_fwd_plan((int)M, (int)N, (int)K);
+                                      int64_t incr, int64_t groups) {
+  cosamd::ConvCfg p =
+      cosamd::conv_fwd_plan((int)M, (int)N, (int)K, (int)groups);
   std::vector<int64_t> out = {p.bm, p.bn, p.waves, p.depth};
   if (!geom.empty()) {
     int g[14];
@@ -1499,7 +1501,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("incr") = -1);
   m.def("conv_fwd_plan", &py_conv_fwd_plan, py::arg("M"), py::arg("N"),
         py::arg("K"), py::arg("geom") = std::vector<int64_t>{},
-        py::arg("incr") = -1);
+        py::arg("incr") = -1, py::arg("groups") = 1);
   m.def("conv_fwd_cfgs", &py_conv_fwd_cfgs);
   m.def("gemm_conv_dw", &py_gemm_conv_dw);
   m.def("gemm_conv_fwd_sc", &py_gemm_conv_fwd_sc);

@@ -46,7 +46,13 @@
 //     COS_CONVQ, else 8 waves depth 2 when w8, else 4 waves.  Narrower
 //     tiles take rows, waves and depth from the sweep in
 //     profiles/alexnet_1gpu_conv_tiles.md (256-row blocks for 48 and 64
-//     columns at large M).  All widths give bit-identical results.
+//     columns at large M).  Tiles of 96 and 128 columns take 256 rows
+//     (8 waves as 4x2, depth 2: a quarter less operand staging per FLOP)
+//     when the launch has at least 384 such blocks over all its groups,
+//     1.5 per CU, and no width is forced
+//     (profiles/alexnet_1gpu_conv_wide.md).  128x192 and 256x192 tiles
+//     exist only with -DCOS_CONV_SWEEP.  All tiles give bit-identical
+//     results.
 //     A grouped convolution is one launch: blockIdx.y is the group, and
 //     three strides move the input channel window, the B rows and the C
 //     columns per group (bias advances by N).
@@ -1135,19 +1141,35 @@ __global__ __launch_bounds__(WAVES * 64, 2) void gemm_kernel(
 // Its state costs registers, and three tiles sit right at the VGPR count
 // their blocks per CU allow (profiles/alexnet_1gpu_conv_tiles.md), so the
 // INCR kernels name that occupancy and the register allocator holds it;
-// the others keep the two blocks per CU of the launch bound.
+// the others keep the two blocks per CU of the launch bound (one for a
+// 64x96 wave tile, whose 96 accumulators leave no room for two).
 template <class Cfg, int DEPTH, bool INCR>
 constexpr int conv_waves_per_simd() {
-  if (!INCR) return 2 * Cfg::WAVES / 4;
+  constexpr int acc = Cfg::MF * Cfg::NF * 4;   // accumulator registers
+  if (!INCR) return (acc >= 96 ? 1 : 2) * Cfg::WAVES / 4;
   constexpr int ring = DEPTH * (Cfg::A_ELEMS + Cfg::B_ELEMS) * 2 +
                        Cfg::TBM * 12;
   int blocks = 160 * 1024 / ring;            // what the LDS allows
   int waves = blocks * Cfg::WAVES / 4;
-  // 32 accumulator + 24 fragment registers: 128x128 8w stops at 6 waves,
-  // 128x128 4w (64 + 32) at 4
-  int cap = Cfg::TBN == 128 ? (Cfg::WAVES == 8 ? 6 : 4) : 8;
+  // what the registers allow, by the wave tile's accumulators (its
+  // fragments and the walk's state come on top): 96 (64x96) fit 256
+  // registers, 48-64 (64x64, 64x48, 32x96) fit 128, 32 (32x64, 64x32) fit
+  // 80, smaller wave tiles fit 64
+  int cap = acc >= 96 ? 2 : acc >= 48 ? 4 : acc >= 32 ? 6 : 8;
   return waves < cap ? waves : cap;
 }
+// the rule above names, for the tiles it was first written for, what it
+// named then (128x128 at 8 waves depth 4 and 2, at 4 waves; 128x96; 256x64)
+static_assert(conv_waves_per_simd<TileCfg<128, 128, 4, 2>, 4, true>() == 4 &&
+              conv_waves_per_simd<TileCfg<128, 128, 4, 2>, 2, true>() == 6 &&
+              conv_waves_per_simd<TileCfg<128, 128, 2, 2>, 2, true>() == 4 &&
+              conv_waves_per_simd<TileCfg<128, 96, 2, 2>, 2, true>() == 4 &&
+              conv_waves_per_simd<TileCfg<128, 96, 4, 2>, 2, true>() == 8 &&
+              conv_waves_per_simd<TileCfg<128, 64, 2, 2>, 2, true>() == 6 &&
+              conv_waves_per_simd<TileCfg<256, 64, 4, 2>, 2, true>() == 6 &&
+              conv_waves_per_simd<TileCfg<128, 48, 4, 1>, 4, true>() == 3 &&
+              conv_waves_per_simd<TileCfg<256, 48, 8, 1>, 2, true>() == 6,
+              "occupancy of the tiles the plan already takes");
 
 template <class Cfg, int DEPTH, bool INCR>
 __global__ __attribute__((
@@ -1650,14 +1672,19 @@ static CGeom make_geom(const int* g) {
 // Every instantiation of gemm_conv_fwd_kernel: CFG_(id, TBM, TBN, WM, WN,
 // DEPTH).  The ids are what gemm_conv_fwd's cfg argument and
 // tools/conv_tile_bench.py name; 0-2 are the fixed 128-wide kernels
-// <8,4>, <8,2> and <4,2>.  Ids 12-17 lost the sweep everywhere
-// (profiles/alexnet_1gpu_conv_tiles.md); they are compiled only with
-// -DCOS_CONV_SWEEP, to repeat it.
+// <8,4>, <8,2> and <4,2>, 12 and 13 the 256-row tiles of 128 and 96
+// columns.  Ids 14-18 lost the sweep everywhere
+// (profiles/alexnet_1gpu_conv_tiles.md, where 18 was 12), and the
+// 192-column tiles 19-21 win nowhere by more than 256x96 does
+// (profiles/alexnet_1gpu_conv_wide.md); they are compiled only with
+// -DCOS_CONV_SWEEP, to repeat the sweeps.  No depth-4 form of 12, 13 or
+// 19-21: their rings of 96 KB would leave one block per CU.
 #ifdef COS_CONV_SWEEP
 #define COS_CONV_SWEEP_CFGS(CFG_)                                           \
-  CFG_(12, 128, 96, 4, 2, 4)  CFG_(13, 256, 96, 4, 2, 2)                    \
   CFG_(14, 256, 64, 4, 1, 2)  CFG_(15, 256, 48, 4, 1, 2)                    \
-  CFG_(16, 128, 96, 2, 2, 4)  CFG_(17, 128, 64, 2, 2, 4)
+  CFG_(16, 128, 96, 2, 2, 4)  CFG_(17, 128, 64, 2, 2, 4)                    \
+  CFG_(18, 128, 96, 4, 2, 4)  CFG_(19, 128, 192, 2, 4, 2)                   \
+  CFG_(20, 128, 192, 4, 2, 2) CFG_(21, 256, 192, 4, 2, 2)
 #else
 #define COS_CONV_SWEEP_CFGS(CFG_)
 #endif
@@ -1668,6 +1695,7 @@ static CGeom make_geom(const int* g) {
   CFG_(6, 128, 64, 4, 2, 2)   CFG_(7, 128, 64, 4, 2, 4)                     \
   CFG_(8, 256, 64, 4, 2, 2)   CFG_(9, 128, 48, 4, 1, 2)                     \
   CFG_(10, 128, 48, 4, 1, 4)  CFG_(11, 256, 48, 8, 1, 2)                    \
+  CFG_(12, 256, 128, 4, 2, 2) CFG_(13, 256, 96, 4, 2, 2)                    \
   COS_CONV_SWEEP_CFGS(CFG_)
 
 struct ConvCfg { int id, bm, bn, waves, depth; };
@@ -1697,15 +1725,25 @@ ConvCfg conv_fwd_cfg(int id) {
 }
 
 // N tile with the least padding, ceil(N/BN)*BN minimal, the wider on a
-// tie; COS_CONV_BN = 48/64/96/128 forces one (0 or unset: automatic).
-static int conv_bn(int N) {
+// tie; COS_CONV_BN = 48/64/96/128 forces one (0 or unset: automatic), and
+// so does 192 in a -DCOS_CONV_SWEEP build, which has tiles of that width.
+static int conv_bn(int N, bool* forced_out) {
   // read per call, unlike COS_CONVQ: conv2d_forward/backward take no tile
   // argument, and the tests flip the width under them inside one process
   const char* e = getenv("COS_CONV_BN");
   int forced = e ? atoi(e) : 0;
+#ifdef COS_CONV_SWEEP
+  const bool ok192 = forced == 192;
+#else
+  const bool ok192 = false;
+  if (forced == 192)
+    throw std::runtime_error("COS_CONV_BN=192: the 192-column tiles are "
+                             "compiled only with -DCOS_CONV_SWEEP");
+#endif
   if (forced != 0 && forced != 48 && forced != 64 && forced != 96 &&
-      forced != 128)
+      forced != 128 && !ok192)
     throw std::runtime_error("COS_CONV_BN must be 0, 48, 64, 96 or 128");
+  *forced_out = forced != 0;
   if (forced) return forced;
   int best = 128, best_pad = (N + 127) / 128 * 128;
   for (int bn : {96, 64, 48}) {
@@ -1715,10 +1753,11 @@ static int conv_bn(int N) {
   return best;
 }
 
-// The configuration gemm_conv_fwd runs [M, N, K] with (N per group).
+// The configuration gemm_conv_fwd runs [M, N, K] with (N per group,
+// `groups` of them in the launch).
 // BN = 128 is the fixed-tile rule: 8 waves for skinny shapes (use_w8),
 // the one-barrier depth-4 ring inside the COS_CONVQ K gate.
-ConvCfg conv_fwd_plan(int M, int N, int K) {
+ConvCfg conv_fwd_plan(int M, int N, int K, int groups) {
   static const int quad = [] {
     // COS_CONVQ: 0 = off, otherwise a max-K gate (1 = "all shapes").
     // Default 1152: same-box A/B is +2.2% CIFAR, neutral AlexNet/
@@ -1737,12 +1776,25 @@ ConvCfg conv_fwd_plan(int M, int N, int K) {
   // with them.  Small M was not swept; it keeps 128 rows and, for 64 and
   // 48 columns, the fixed tile's depth rule (the COS_CONVQ gate).
   bool big_m = M >= 8192;
+  bool forced;
+  int bn = conv_bn(N, &forced);
+  // 256-row blocks for 96 and 128 columns (a quarter less operand staging
+  // per FLOP) where the launch has at least 1.5 of them per CU of the 256:
+  // in profiles/alexnet_1gpu_conv_wide.md they won at 507 blocks and more
+  // and lost at 338, where two per CU leave a third of the chip idle.  A
+  // forced width names the 128-row kernels, as it always has.
+  int64_t tall_blocks = (int64_t)((M + 255) / 256) * ((N + bn - 1) / bn) *
+                        (groups > 0 ? groups : 1);
+  bool tall = big_m && !forced && tall_blocks >= 384;
   int id;
-  switch (conv_bn(N)) {
-    case 96: id = w8 ? 4 : 3; break;
+  switch (bn) {
+#ifdef COS_CONV_SWEEP
+    case 192: id = 19; break;
+#endif
+    case 96: id = tall ? 13 : w8 ? 4 : 3; break;
     case 64: id = big_m ? 8 : w8 ? (q ? 7 : 6) : 5; break;
     case 48: id = big_m ? 11 : q ? 10 : 9; break;
-    default: id = w8 ? (q ? 0 : 1) : 2; break;
+    default: id = tall ? 12 : w8 ? (q ? 0 : 1) : 2; break;
   }
   return kConvCfgs[id];
 }
@@ -1788,7 +1840,7 @@ void gemm_conv_fwd(const void* X, const void* B, void* C,
                              "at least two");
   if (cfg >= kNumConvCfgs)
     throw std::runtime_error("gemm_conv_fwd: no such configuration");
-  ConvCfg p = cfg >= 0 ? kConvCfgs[cfg] : conv_fwd_plan(M, N, K);
+  ConvCfg p = cfg >= 0 ? kConvCfgs[cfg] : conv_fwd_plan(M, N, K, groups);
   int mblocks = (M + p.bm - 1) / p.bm, nblocks = (N + p.bn - 1) / p.bn;
   dim3 grid(mblocks * nblocks, max(1, groups));
   // the 16-byte epilogue needs whole, aligned 8-channel runs

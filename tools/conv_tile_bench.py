@@ -14,6 +14,9 @@ has no conv_fwd_plan).
   python tools/conv_tile_bench.py --grouped       # all groups, one launch
   python tools/conv_tile_bench.py --sweep         # every configuration id
   python tools/conv_tile_bench.py --sweep --vec 0 # ... element-wise epilogue
+  python tools/conv_tile_bench.py --grouped --cfgs=-1,12,13 --rounds 2
+                                  # the plan's choice against ids 12 and 13,
+                                  # the whole list timed twice, alternated
   python tools/conv_tile_bench.py --grouped --incr 0  # divide-form A staging
   COS_CONV_BN=128 python tools/conv_tile_bench.py # the fixed 128-wide tile
 
@@ -134,6 +137,12 @@ def main():
                     help="one launch for all groups of a layer")
     ap.add_argument("--sweep", action="store_true",
                     help="time every configuration id, not the chosen one")
+    ap.add_argument("--cfgs", default="",
+                    help="comma-separated configuration ids to time per "
+                         "shape (-1: the build's choice)")
+    ap.add_argument("--rounds", type=int, default=1,
+                    help="time the list of configurations this many times "
+                         "per shape, one after the other")
     ap.add_argument("--vec", type=int, default=-1,
                     help="epilogue: 0 element-wise, 1 16-byte stores, "
                          "-1 the build's choice")
@@ -156,8 +165,13 @@ def main():
     print("|---|---|---|---|---|---|---|---|---|---|")
     for row in ROWS:
         sets = _buffers(row, dev)
-        table = ext.conv_fwd_cfgs() if args.sweep else None
-        for cfg in (range(len(table)) if args.sweep else [-1]):
+        table = ext.conv_fwd_cfgs() if args.sweep or args.cfgs else None
+        ids = [-1]
+        if args.sweep:
+            ids = list(range(len(table)))
+        elif args.cfgs:
+            ids = [int(c) for c in args.cfgs.split(",")]
+        for cfg in ids * args.rounds:
             med, lo, hi = _time(ext, row, sets, zpage, args.grouped, cfg,
                                 args.vec, args.incr)
             launches = 1 if args.grouped else row["groups"]
@@ -165,7 +179,7 @@ def main():
             bn, shape = 128, "128x128"
             if cfg >= 0 or plan is not None:
                 bm, bn, waves, depth = table[cfg] if cfg >= 0 else \
-                    plan(row["M"], row["N"], row["K"])
+                    plan(row["M"], row["N"], row["K"], groups=gmul)
                 shape = f"{bm}x{bn} {waves}w d{depth}"
             useful = 2.0 * row["M"] * row["N"] * row["K"] * gmul
             padded = 2.0 * row["M"] * _pad(row["N"], bn) * row["K"] * gmul
@@ -180,7 +194,7 @@ def main():
                   f"{r['padded_tfs']:.0f} |", flush=True)
         del sets
         torch.cuda.empty_cache()
-    if not args.sweep:
+    if not args.sweep and not args.cfgs and args.rounds == 1:
         per_step = sum(r["us"] * r["launches"] for r in results)
         print(f"\nper step (us x launches, summed): {per_step:.0f} us")
     if args.out:

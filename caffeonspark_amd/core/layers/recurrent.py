@@ -114,6 +114,25 @@ class LSTMLayer(Layer):
             return False
         return ops.gpu_op("lstm_step_ok")(N, self.d, self.h, Ds, tensors)
 
+    def _step_loop(self, x, cont, xg, w_hc, h_prev, c_prev):
+        """ops.fc_forward + ops.lstm_unit_forward per step over xg [T,N,4H]
+        from the state (h_prev, c_prev).  Returns hs, the backward cache
+        (self._cache's layout) and the final (h_T, c_T)."""
+        T, N = xg.shape[0], xg.shape[1]
+        hs, caches, h_prevs, c_prevs = [], [], [], []
+        for t in range(T):
+            cont_t = cont[t].reshape(N, 1).to(x.dtype)
+            h_in = h_prev * cont_t
+            gates = xg[t] + ops.fc_forward(h_in, w_hc, None)
+            c_t, h_t, cache = ops.lstm_unit_forward(c_prev, gates, cont[t])
+            h_prevs.append(h_in)
+            c_prevs.append(c_prev)
+            caches.append(cache)
+            hs.append(h_t)
+            c_prev = c_t.float()
+            h_prev = h_t
+        return hs, (x, cont, caches, h_prevs, c_prevs, hs), (h_prev, c_prev)
+
     def _forward_step(self, bottom, top):
         """Per-step loop from a given start state: serves expose_hidden
         and stateful layers.  T == 1 on the bf16 GPU path is one fused
@@ -159,20 +178,8 @@ class LSTMLayer(Layer):
             xg = ops.fc_forward(x2, w_xc, b_c).reshape(T, N, 4 * H)
             if self.static:
                 xg = xg + ops.fc_forward(xs, w_xsc, None).unsqueeze(0)
-            hs, caches, h_prevs, c_prevs = [], [], [], []
-            for t in range(T):
-                cont_t = cont[t].reshape(N, 1).to(x.dtype)
-                h_in = h_prev * cont_t
-                gates = xg[t] + ops.fc_forward(h_in, w_hc, None)
-                c_t, h_t, cache = ops.lstm_unit_forward(c_prev, gates,
-                                                        cont[t])
-                h_prevs.append(h_in)
-                c_prevs.append(c_prev)
-                caches.append(cache)
-                hs.append(h_t)
-                c_prev = c_t = c_t.float()
-                h_prev = h_t
-            self._cache = (x, cont, caches, h_prevs, c_prevs, hs)
+            hs, self._cache, (h_t, c_t) = self._step_loop(
+                x, cont, xg, w_hc, h_prev, c_prev)
         # h_t and c_t are fresh tensors: earlier tops keep their values
         top[0].data = hs[0].reshape(1, N, H) if T == 1 \
             else torch.stack(hs, dim=0)
@@ -205,23 +212,11 @@ class LSTMLayer(Layer):
             top[0].data = y
             self._cache = ("seq", x, cont, seq_cache)
             return 0.0
-        h_prev = torch.zeros(N, H, dtype=x.dtype, device=x.device)
-        c_prev = torch.zeros(N, H, dtype=torch.float32, device=x.device)
-        hs, caches, h_prevs, c_prevs = [], [], [], []
-        for t in range(T):
-            cont_t = cont[t].reshape(N, 1).to(x.dtype)
-            h_in = h_prev * cont_t
-            gates = xg[t] + ops.fc_forward(h_in, w_hc, None)
-            c_t, h_t, cache = ops.lstm_unit_forward(c_prev, gates, cont[t])
-            h_prevs.append(h_in)
-            c_prevs.append(c_prev)
-            caches.append(cache)
-            hs.append(h_t)
-            c_prev = c_t.float()
-            h_prev = h_t
-        y = torch.stack(hs, dim=0)
-        top[0].data = y
-        self._cache = (x, cont, caches, h_prevs, c_prevs, hs)
+        hs, self._cache, _ = self._step_loop(
+            x, cont, xg, w_hc,
+            torch.zeros(N, H, dtype=x.dtype, device=x.device),
+            torch.zeros(N, H, dtype=torch.float32, device=x.device))
+        top[0].data = torch.stack(hs, dim=0)
         return 0.0
 
     def backward(self, top, propagate_down, bottom):

@@ -13,16 +13,7 @@
 
 namespace cosamd {
 
-typedef unsigned short u16;
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float ldbf(const u16* p) {
-  return bf2f(*reinterpret_cast<const bf16*>(p));
-}
-__device__ __forceinline__ void stbf(u16* p, float v) {
-  bf16 b = f2bf(v);
-  *p = *reinterpret_cast<u16*>(&b);
-}
 
 // two-moment reduce: out0[c] += sum(w0), out1[c] += sum(w1)
 // MODE 0: a = x:     w0 = x,  w1 = x*x      (forward stats)

@@ -34,6 +34,16 @@ __device__ __forceinline__ bf16 f2bf(float v) {
   return __float2bfloat16(v);
 }
 
+// bf16 tensors travel as raw 16-bit words; scalar load / round-and-store
+typedef unsigned short u16;
+__device__ __forceinline__ float ldbf(const u16* p) {
+  return bf2f(*reinterpret_cast<const bf16*>(p));
+}
+__device__ __forceinline__ void stbf(u16* p, float v) {
+  bf16 b = f2bf(v);
+  *p = *reinterpret_cast<u16*>(&b);
+}
+
 // bijective XCD-aware blockIdx swizzle (8 XCDs on MI355X): contiguous
 // chunks of the grid land on one XCD so neighboring tiles share L2.
 __device__ __forceinline__ int xcd_swizzle(int bid, int nwg) {

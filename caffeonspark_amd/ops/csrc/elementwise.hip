@@ -4,21 +4,13 @@
 // All bf16 traffic is vectorized 8-wide (G13: scalar bf16 ~2x slower).
 
 #include "common.h"
+#include "lstm_cell.h"
 
 namespace cosamd {
 
-typedef unsigned short u16;
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float ldbf(const u16* p) {
-  return bf2f(*reinterpret_cast<const bf16*>(p));
-}
-__device__ __forceinline__ void stbf(u16* p, float v) {
-  bf16 b = f2bf(v);
-  *p = *reinterpret_cast<u16*>(&b);
-}
 
 // ---------------------------------------------------------------- ReLU
 
@@ -717,7 +709,8 @@ __global__ void colsum_kernel(const u16* __restrict__ in, float* __restrict__ ou
 }
 
 // --------------------------------------------------------------- LSTM unit
-// gates [N,4H] pre-activation (i,f,o,g); fp32 cell state.
+// gates [N,4H] pre-activation (i,f,o,g); fp32 cell state.  The cell math
+// is lstm_cell.h's; bwd recomputes tanh(c) from c_out.
 
 __global__ void lstm_unit_fwd_kernel(
     const float* __restrict__ c_prev, const u16* __restrict__ gates,
@@ -729,18 +722,14 @@ __global__ void lstm_unit_fwd_kernel(
     int64_t row = i / H;
     int hh = i % H;
     const u16* g = gates + row * 4 * H;
-    float gi = 1.f / (1.f + __expf(-ldbf(g + hh)));
-    float gf = 1.f / (1.f + __expf(-ldbf(g + H + hh)));
-    float go = 1.f / (1.f + __expf(-ldbf(g + 2 * H + hh)));
-    float gg = tanhf(ldbf(g + 3 * H + hh));
-    float ct = ldbf(cont + row);
-    float c = gf * c_prev[i] * ct + gi * gg;
-    float tc = tanhf(c);
-    c_out[i] = c;
-    stbf(h_out + i, go * tc);
+    LstmCellFwd r = lstm_cell_fwd(
+        ldbf(g + hh), ldbf(g + H + hh), ldbf(g + 2 * H + hh),
+        ldbf(g + 3 * H + hh), c_prev[i], ldbf(cont + row));
+    c_out[i] = r.c;
+    stbf(h_out + i, r.h);
     float* a = act + row * 4 * H;
-    a[hh] = gi; a[H + hh] = gf; a[2 * H + hh] = go; a[3 * H + hh] = gg;
-    // tc recomputed in bwd from c_out
+    a[hh] = r.gi; a[H + hh] = r.gf; a[2 * H + hh] = r.go;
+    a[3 * H + hh] = r.gg;
   }
 }
 
@@ -755,21 +744,15 @@ __global__ void lstm_unit_bwd_kernel(
     int64_t row = i / H;
     int hh = i % H;
     const float* a = act + row * 4 * H;
-    float gi = a[hh], gf = a[H + hh], go = a[2 * H + hh], gg = a[3 * H + hh];
-    float tc = tanhf(c_out[i]);
-    float ct = ldbf(cont + row);
-    float dhv = ldbf(dh + i);
-    float dc = dc_next[i] + dhv * go * (1.f - tc * tc);
-    float dov = dhv * tc;
-    float div = dc * gg;
-    float dgv = dc * gi;
-    float dfv = dc * c_prev[i] * ct;
-    dc_prev[i] = dc * gf * ct;
+    LstmCellBwd r = lstm_cell_bwd(
+        a[hh], a[H + hh], a[2 * H + hh], a[3 * H + hh], c_out[i], c_prev[i],
+        ldbf(cont + row), ldbf(dh + i), dc_next[i]);
+    dc_prev[i] = r.dc_prev;
     u16* dg = dgates + row * 4 * H;
-    stbf(dg + hh, div * gi * (1.f - gi));
-    stbf(dg + H + hh, dfv * gf * (1.f - gf));
-    stbf(dg + 2 * H + hh, dov * go * (1.f - go));
-    stbf(dg + 3 * H + hh, dgv * (1.f - gg * gg));
+    stbf(dg + hh, r.di);
+    stbf(dg + H + hh, r.df);
+    stbf(dg + 2 * H + hh, r.dO);
+    stbf(dg + 3 * H + hh, r.dg);
   }
 }
 

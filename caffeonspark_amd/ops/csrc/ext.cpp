@@ -102,12 +102,12 @@ void dw_unpack_s2d(const float* dwp, float* arena, int Kout, int Cg, int R,
                    int S, int st, int Kpad, bool accumulate,
                    hipStream_t stream);
 int lstm_persist_fwd(const void* xg, const void* w_hc, const void* cont,
-                     void* h, float* c, float* act, void* h_in, float* hg,
+                     void* h, float* c, float* act, void* h_in,
                      int T, int N, int H, void* bar, hipStream_t stream);
 int lstm_persist_bwd(const void* dy, const void* w_hcT, const void* cont,
                      const void* h, const float* c, const float* act,
-                     void* dxg, float* dh_acc, float* dc_a, float* dc_b,
-                     int T, int N, int H, void* bar, hipStream_t stream);
+                     void* dxg, int T, int N, int H, void* bar,
+                     hipStream_t stream);
 void wino_conv(const void* x, const float* w, const float* bias, void* y,
                void* U, void* V, void* Mbuf, int N, int H, int W, int Cin,
                int K, int wK, int wC, int u_rows_alloc, bool flip,
@@ -1148,25 +1148,20 @@ void py_dw_unpack_s2d(Tensor dwp, Tensor arena, int64_t Kout, int64_t Cg,
 
 int64_t py_lstm_persist_fwd(Tensor xg, Tensor w_hc, Tensor cont,
                             Tensor h, Tensor c, Tensor act, Tensor h_in,
-                            Tensor hg, int64_t T, int64_t N, int64_t H,
-                            Tensor bar) {
+                            int64_t T, int64_t N, int64_t H, Tensor bar) {
   return cosamd::lstm_persist_fwd(
       xg.data_ptr(), w_hc.data_ptr(), cont.data_ptr(), h.data_ptr(),
       c.data_ptr<float>(), act.data_ptr<float>(), h_in.data_ptr(),
-      hg.data_ptr<float>(), (int)T, (int)N, (int)H, bar.data_ptr(),
-      cur_stream());
+      (int)T, (int)N, (int)H, bar.data_ptr(), cur_stream());
 }
 
 int64_t py_lstm_persist_bwd(Tensor dy, Tensor w_hcT, Tensor cont,
                             Tensor h, Tensor c, Tensor act, Tensor dxg,
-                            Tensor dh_acc, Tensor dc_a, Tensor dc_b,
                             int64_t T, int64_t N, int64_t H, Tensor bar) {
   return cosamd::lstm_persist_bwd(
       dy.data_ptr(), w_hcT.data_ptr(), cont.data_ptr(), h.data_ptr(),
       c.data_ptr<float>(), act.data_ptr<float>(), dxg.data_ptr(),
-      dh_acc.data_ptr<float>(), dc_a.data_ptr<float>(),
-      dc_b.data_ptr<float>(), (int)T, (int)N, (int)H, bar.data_ptr(),
-      cur_stream());
+      (int)T, (int)N, (int)H, bar.data_ptr(), cur_stream());
 }
 
 void py_transpose(Tensor in, Tensor out, int64_t R, int64_t C) {

@@ -6,9 +6,9 @@
 // stationary in VGPR MFMA fragments, ~128 VGPRs/lane), so
 //   * gate sums never cross blocks: no fp32 atomics, no gate buffer --
 //     cross-wave K-partials reduce through LDS inside the block;
-//   * the LSTM unit math for the slice is block-local, and the cell
-//     state c (forward) / dc and dh (backward) live in LDS across the
-//     whole sequence;
+//   * the LSTM unit math for the slice (lstm_cell.h, shared with the
+//     other routes) is block-local, and the cell state c (forward) / dc
+//     and dh (backward) live in LDS across the whole sequence;
 //   * exactly ONE grid barrier per timestep (between writing h_in_{t+1}
 //     / dxg_t and the other blocks' reads of them) -- v1's
 //     4H-column-partitioned design needed two plus 16 MB/t of atomics.
@@ -21,22 +21,14 @@
 // §5 long-context: time-major, cont gating).
 
 #include "common.h"
+#include "lstm_cell.h"
 
 namespace cosamd {
 
-typedef unsigned short u16;
 typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 namespace {
-
-__device__ __forceinline__ float ldbf(const u16* p) {
-  return bf2f(*reinterpret_cast<const bf16*>(p));
-}
-__device__ __forceinline__ void stbf(u16* p, float v) {
-  bf16 b = f2bf(v);
-  *p = *reinterpret_cast<u16*>(&b);
-}
 
 // Grid barrier with store-slot arrival (each block plain-stores its
 // running barrier index into its own slot; block 0's threads poll all
@@ -103,6 +95,55 @@ __device__ __forceinline__ bool grid_sync(unsigned* bar, unsigned nblk,
                            __HIP_MEMORY_SCOPE_AGENT) == 0;
 }
 
+// One k-step's A fragments for the 64-row tile: a[mf] = 8 elements at
+// column k of row mf*16 + lrow of A (row pitch ld), zero past column kmax.
+__device__ __forceinline__ void load_a(bf16x8v (&a)[4], const u16* A, int ld,
+                                       int kmax, int k, int lrow) {
+#pragma unroll
+  for (int mf = 0; mf < 4; ++mf) {
+    int m = mf * 16 + lrow;
+    if (k + 8 <= kmax) {
+      a[mf] = *reinterpret_cast<const bf16x8v*>(A + (int64_t)m * ld + k);
+    } else {
+      bf16 z = f2bf(0.f);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) a[mf][j] = z;
+    }
+  }
+}
+
+// Sum the four waves' k-partials (NV floats per lane, held as NV/4 MFMA
+// accumulators) into wave 0's registers, pairwise through LDS: waves 1
+// and 3 hand theirs to 0 and 2 (red0, red1), then 2 hands its sum to 0
+// (red0).  Three barriers; the caller scatters wave 0's acc and barriers.
+template <int NV>
+__device__ __forceinline__ void wave_reduce(f32x4v (&acc)[NV / 4],
+                                            f32x4v* red0, f32x4v* red1,
+                                            int wave, int lane) {
+  constexpr int NQ = NV / 4;
+  f32x4v* to0 = red0 + lane * NQ;
+  f32x4v* mine = (wave >> 1) ? red1 + lane * NQ : to0;
+  if (wave & 1) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) mine[q] = acc[q];
+  }
+  __syncthreads();
+  if (!(wave & 1)) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) acc[q] += mine[q];
+  }
+  __syncthreads();
+  if (wave == 2) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) to0[q] = acc[q];
+  }
+  __syncthreads();
+  if (wave == 0) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) acc[q] += to0[q];
+  }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------- forward
@@ -115,7 +156,7 @@ __global__ __launch_bounds__(256, 1) void lstm_persist_fwd_kernel(
     float* __restrict__ c, float* __restrict__ act,
     u16* __restrict__ h_in, int T, int N, int H,
     unsigned* bar, int* err) {
-  __shared__ float red0[64 * 16 * 4], red1[64 * 16 * 4];  // wave partials
+  __shared__ f32x4v red0[64 * 16], red1[64 * 16];  // wave partials
   __shared__ float gates[64 * 64];                // [n][strip*16 + jj]
   __shared__ float c_lds[64 * 16];                // cell state, persists
   int H4 = 4 * H;
@@ -153,86 +194,37 @@ __global__ __launch_bounds__(256, 1) void lstm_persist_fwd_kernel(
   for (int t = 0; t < T; ++t) {
     // ---- gate GEMM over the full K for this block's 64 gate columns
     const u16* A = h_in + (int64_t)t * nh;
-    f32x4v acc[4][4] = {};    // [mf][strip]
+    f32x4v acc[16] = {};      // [mf * 4 + strip]
     // software-pipelined a-loads: fetch ks+1 while ks's MFMAs run (the
     // 4-MFMA bursts are too short to hide the L2 load chain otherwise)
     bf16x8v a_cur[4], a_nxt[4];
-    auto load_a = [&](bf16x8v (&a)[4], int ks) {
-      int k = kw0 + ks * 32 + lk8;
-#pragma unroll
-      for (int mf = 0; mf < 4; ++mf) {
-        int m = mf * 16 + lrow;
-        if (k + 8 <= H) {
-          a[mf] = *reinterpret_cast<const bf16x8v*>(
-              A + (int64_t)m * H + k);
-        } else {
-          bf16 z = f2bf(0.f);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) a[mf][j] = z;
-        }
-      }
-    };
-    load_a(a_cur, 0);
+    load_a(a_cur, A, H, H, kw0 + lk8, lrow);
     for (int ks = 0; ks < ksteps; ++ks) {
-      if (ks + 1 < ksteps) load_a(a_nxt, ks + 1);
+      if (ks + 1 < ksteps)
+        load_a(a_nxt, A, H, H, kw0 + (ks + 1) * 32 + lk8, lrow);
 #pragma unroll
       for (int mf = 0; mf < 4; ++mf)
 #pragma unroll
         for (int s = 0; s < 4; ++s)
-          acc[mf][s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a_cur[mf], wf[s][ks < 8 ? ks : 0], acc[mf][s], 0, 0, 0);
+          acc[mf * 4 + s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a_cur[mf], wf[s][ks < 8 ? ks : 0], acc[mf * 4 + s], 0, 0, 0);
 #pragma unroll
       for (int mf = 0; mf < 4; ++mf) a_cur[mf] = a_nxt[mf];
     }
-    // ---- cross-wave reduce into gates[] (pairwise through LDS)
-    {
-      float* mybuf = (wave >> 1) ? red1 : red0;
-      if (wave & 1) {
+    // ---- cross-wave reduce, wave 0 scatters the sums into gates[]
+    wave_reduce<64>(acc, red0, red1, wave, lane);
+    if (wave == 0) {
 #pragma unroll
-        for (int mf = 0; mf < 4; ++mf)
+      for (int mf = 0; mf < 4; ++mf)
 #pragma unroll
-          for (int s = 0; s < 4; ++s)
+        for (int s = 0; s < 4; ++s)
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-              mybuf[(lane * 16 + mf * 4 + s) * 4 + r] = acc[mf][s][r];
-      }
-      __syncthreads();
-      if (!(wave & 1)) {
-#pragma unroll
-        for (int mf = 0; mf < 4; ++mf)
-#pragma unroll
-          for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              acc[mf][s][r] += mybuf[(lane * 16 + mf * 4 + s) * 4 + r];
-      }
-      __syncthreads();
-      if (wave == 2) {
-#pragma unroll
-        for (int mf = 0; mf < 4; ++mf)
-#pragma unroll
-          for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              red0[(lane * 16 + mf * 4 + s) * 4 + r] = acc[mf][s][r];
-      }
-      __syncthreads();
-      if (wave == 0) {
-#pragma unroll
-        for (int mf = 0; mf < 4; ++mf)
-#pragma unroll
-          for (int s = 0; s < 4; ++s) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              int row = (lane >> 4) * 4 + mf * 16 + r;
-              float v = acc[mf][s][r] +
-                        red0[(lane * 16 + mf * 4 + s) * 4 + r];
-              gates[row * 64 + s * 16 + lrow] = v;
-            }
+          for (int r = 0; r < 4; ++r) {
+            int row = (lane >> 4) * 4 + mf * 16 + r;
+            gates[row * 64 + s * 16 + lrow] = acc[mf * 4 + s][r];
           }
-      }
-      __syncthreads();
     }
+    __syncthreads();
 
     // ---- block-local fused unit over (n < N) x (16 slice cols)
     const u16* cont_t = cont + (int64_t)t * N;
@@ -249,26 +241,19 @@ __global__ __launch_bounds__(256, 1) void lstm_persist_fwd_kernel(
       int jg = j0 + jj;
       if (jg >= H) continue;
       int64_t g0 = (int64_t)n * H4 + jg;
-      float gi = 1.f / (1.f + __expf(-(ldbf(xg_t + g0) +
-                                       gates[n * 64 + jj])));
-      float gf = 1.f / (1.f + __expf(-(ldbf(xg_t + g0 + H) +
-                                       gates[n * 64 + 16 + jj])));
-      float go = 1.f / (1.f + __expf(-(ldbf(xg_t + g0 + 2 * H) +
-                                       gates[n * 64 + 32 + jj])));
-      float gg = tanhf(ldbf(xg_t + g0 + 3 * H) +
-                       gates[n * 64 + 48 + jj]);
-      float ct = ldbf(cont_t + n);
-      float cp = c_lds[i];
-      float cv = gf * cp * ct + gi * gg;
-      c_lds[i] = cv;
+      const float* hg = gates + n * 64 + jj;
+      LstmCellFwd r = lstm_cell_fwd(
+          ldbf(xg_t + g0) + hg[0], ldbf(xg_t + g0 + H) + hg[16],
+          ldbf(xg_t + g0 + 2 * H) + hg[32],
+          ldbf(xg_t + g0 + 3 * H) + hg[48], c_lds[i], ldbf(cont_t + n));
+      c_lds[i] = r.c;
       int64_t hi = (int64_t)n * H + jg;
-      c_t[hi] = cv;
-      float hv = go * tanhf(cv);
-      stbf(h_t + hi, hv);
+      c_t[hi] = r.c;
+      stbf(h_t + hi, r.h);
       float* ap = act_t + g0;
-      ap[0] = gi; ap[H] = gf; ap[2 * H] = go; ap[3 * H] = gg;
+      ap[0] = r.gi; ap[H] = r.gf; ap[2 * H] = r.go; ap[3 * H] = r.gg;
       if (h_in_next != nullptr)
-        stbf(h_in_next + hi, hv * ldbf(cont_next + n));
+        stbf(h_in_next + hi, r.h * ldbf(cont_next + n));
     }
     if (!grid_sync(bar, nblk, err, ++sync_idx)) {
       if (threadIdx.x == 0) h[(int64_t)t * nh] = 0x7FC0;  // bf16 NaN
@@ -287,7 +272,7 @@ __global__ __launch_bounds__(256, 1) void lstm_persist_bwd_kernel(
     const float* __restrict__ c, const float* __restrict__ act,
     u16* __restrict__ dxg, int T, int N, int H,
     unsigned* bar, int* err) {
-  __shared__ float red0[64 * 16], red1[64 * 16];
+  __shared__ f32x4v red0[64 * 4], red1[64 * 4];
   __shared__ float dh_lds[64 * 16];
   __shared__ float dc_lds[64 * 16];
   int H4 = 4 * H;
@@ -340,23 +325,18 @@ __global__ __launch_bounds__(256, 1) void lstm_persist_bwd_kernel(
       int64_t g0 = (int64_t)n * H4 + jg;
       int64_t hi = (int64_t)n * H + jg;
       const float* a = act_t + g0;
-      float gi = a[0], gf = a[H], go = a[2 * H], gg = a[3 * H];
-      float tc = tanhf(c_t[hi]);
-      float ct = ldbf(cont_t + n);
       float dhrec = (t + 1 < T) ? dh_lds[i] * ldbf(cont_t1 + n) : 0.f;
       float dhv = ldbf(dy_t + hi) + dhrec;
-      float dc = dc_lds[i] + dhv * go * (1.f - tc * tc);
-      float dov = dhv * tc;
-      float div = dc * gg;
-      float dgv = dc * gi;
       float cp = (c_prev != nullptr) ? c_prev[hi] : 0.f;
-      float dfv = dc * cp * ct;
-      dc_lds[i] = dc * gf * ct;    // dc for t-1 (slice-local)
+      LstmCellBwd r = lstm_cell_bwd(
+          a[0], a[H], a[2 * H], a[3 * H], c_t[hi], cp, ldbf(cont_t + n),
+          dhv, dc_lds[i]);
+      dc_lds[i] = r.dc_prev;       // dc for t-1 (slice-local)
       u16* dg = dxg_t + g0;
-      stbf(dg, div * gi * (1.f - gi));
-      stbf(dg + H, dfv * gf * (1.f - gf));
-      stbf(dg + 2 * H, dov * go * (1.f - go));
-      stbf(dg + 3 * H, dgv * (1.f - gg * gg));
+      stbf(dg, r.di);
+      stbf(dg + H, r.df);
+      stbf(dg + 2 * H, r.dO);
+      stbf(dg + 3 * H, r.dg);
     }
     if (!grid_sync(bar, nblk, err, ++sync_idx)) {
       if (threadIdx.x == 0) dxg[(int64_t)t * N * H4] = 0x7FC0;
@@ -367,24 +347,10 @@ __global__ __launch_bounds__(256, 1) void lstm_persist_bwd_kernel(
     if (t > 0) {
       f32x4v acc[4] = {};     // [mf] x 16 cols
       bf16x8v a_cur[4], a_nxt[4];
-      auto load_a = [&](bf16x8v (&a)[4], int ks) {
-        int k = kw0 + ks * 32 + lk8;
-#pragma unroll
-        for (int mf = 0; mf < 4; ++mf) {
-          int m = mf * 16 + lrow;
-          if (k + 8 <= H4) {
-            a[mf] = *reinterpret_cast<const bf16x8v*>(
-                dxg_t + (int64_t)m * H4 + k);
-          } else {
-            bf16 z = f2bf(0.f);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) a[mf][j] = z;
-          }
-        }
-      };
-      load_a(a_cur, 0);
+      load_a(a_cur, dxg_t, H4, H4, kw0 + lk8, lrow);
       for (int ks = 0; ks < ksteps; ++ks) {
-        if (ks + 1 < ksteps) load_a(a_nxt, ks + 1);
+        if (ks + 1 < ksteps)
+          load_a(a_nxt, dxg_t, H4, H4, kw0 + (ks + 1) * 32 + lk8, lrow);
 #pragma unroll
         for (int mf = 0; mf < 4; ++mf)
           acc[mf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -392,42 +358,16 @@ __global__ __launch_bounds__(256, 1) void lstm_persist_bwd_kernel(
 #pragma unroll
         for (int mf = 0; mf < 4; ++mf) a_cur[mf] = a_nxt[mf];
       }
-      // cross-wave reduce -> dh_lds
-      float* mybuf = (wave >> 1) ? red1 : red0;
-      if (wave & 1) {
-#pragma unroll
-        for (int mf = 0; mf < 4; ++mf)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            mybuf[(lane * 4 + mf) * 4 + r] = acc[mf][r];
-      }
-      __syncthreads();
-      if (!(wave & 1)) {
-#pragma unroll
-        for (int mf = 0; mf < 4; ++mf)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            acc[mf][r] += mybuf[(lane * 4 + mf) * 4 + r];
-      }
-      __syncthreads();
-      if (wave == 2) {
-#pragma unroll
-        for (int mf = 0; mf < 4; ++mf)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            red0[(lane * 4 + mf) * 4 + r] = acc[mf][r];
-      }
-      __syncthreads();
+      // cross-wave reduce, wave 0 scatters the sums into dh_lds
+      wave_reduce<16>(acc, red0, red1, wave, lane);
       if (wave == 0) {
 #pragma unroll
-        for (int mf = 0; mf < 4; ++mf) {
+        for (int mf = 0; mf < 4; ++mf)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             int row = (lane >> 4) * 4 + mf * 16 + r;
-            dh_lds[row * 16 + lrow] =
-                acc[mf][r] + red0[(lane * 4 + mf) * 4 + r];
+            dh_lds[row * 16 + lrow] = acc[mf][r];
           }
-        }
       }
       __syncthreads();
     }
@@ -435,15 +375,12 @@ __global__ __launch_bounds__(256, 1) void lstm_persist_bwd_kernel(
 }
 
 // --------------------------------------------------------------- hosts
-// hg / dh / dc scratch buffers from the v1 API are unused (state lives
-// in LDS); kept in the signatures so the bindings stay stable.
 // returns 0 ok, 1 = not applicable (shape); watchdog aborts are read
 // asynchronously from bar[258] by the Python glue.
 
 int lstm_persist_fwd(const void* xg, const void* w_hc, const void* cont,
-                     void* h, float* c, float* act, void* h_in, float* hg,
+                     void* h, float* c, float* act, void* h_in,
                      int T, int N, int H, void* bar, hipStream_t stream) {
-  (void)hg;
   if (N > 64 || H % 8 != 0 || H > 1024) return 1;  // wf[4][8] k-window
   int nblk = (H + 15) / 16;
   if (nblk < 2 || nblk > 256) return 1;
@@ -458,9 +395,8 @@ int lstm_persist_fwd(const void* xg, const void* w_hc, const void* cont,
 
 int lstm_persist_bwd(const void* dy, const void* w_hcT, const void* cont,
                      const void* h, const float* c, const float* act,
-                     void* dxg, float* dh_acc, float* dc_a, float* dc_b,
-                     int T, int N, int H, void* bar, hipStream_t stream) {
-  (void)dh_acc; (void)dc_a; (void)dc_b;
+                     void* dxg, int T, int N, int H, void* bar,
+                     hipStream_t stream) {
   if (N > 64 || H % 8 != 0 || H > 1024) return 1;  // wf[32] k-window
   int nblk = (H + 15) / 16;
   if (nblk < 2 || nblk > 256) return 1;

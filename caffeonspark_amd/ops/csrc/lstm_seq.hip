@@ -2,16 +2,16 @@
 // host code (3 kernel launches per timestep, no Python/torch dispatch in
 // the loop).  The input GEMM (x @ W_xc + b for all T) and the big weight
 // gradients are done outside as single large GEMMs; this file handles the
-// serial part: per-step hidden GEMM + fused LSTM unit.
+// serial part: per-step hidden GEMM + fused LSTM unit (the cell itself is
+// lstm_cell.h's, shared with the other routes).
 //
 // Reference: the recurrent path of lrcn_cos.prototxt (SURVEY.md §5
 // "Long-context": time-major layout, cont gating, fused gate kernels).
 
 #include "common.h"
+#include "lstm_cell.h"
 
 namespace cosamd {
-
-typedef unsigned short u16;
 
 void gemm_bf16(const void* A, const void* B, void* C, const float* bias,
                int M, int N, int K, int lda, int ldb, int ldc,
@@ -19,21 +19,13 @@ void gemm_bf16(const void* A, const void* B, void* C, const float* bias,
                bool relu, float alpha, int m_alloc, int n_alloc,
                hipStream_t stream);
 
-__device__ __forceinline__ float ldbf_(const u16* p) {
-  return bf2f(*reinterpret_cast<const bf16*>(p));
-}
-__device__ __forceinline__ void stbf_(u16* p, float v) {
-  bf16 b = f2bf(v);
-  *p = *reinterpret_cast<u16*>(&b);
-}
-
 // h_in[n][h] = h_prev[n][h] * cont[n]
 __global__ void rowscale_kernel(const u16* __restrict__ x,
                                 const u16* __restrict__ s,
                                 u16* __restrict__ y, int64_t n, int H) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
        i < n; i += (int64_t)gridDim.x * blockDim.x)
-    stbf_(y + i, ldbf_(x + i) * ldbf_(s + i / H));
+    stbf(y + i, ldbf(x + i) * ldbf(s + i / H));
 }
 
 // h_in[n][h] = h_prev[n][h] * cont[n], fp32 source (split-K GEMM out)
@@ -42,7 +34,7 @@ __global__ void rowscale_f32_kernel(const float* __restrict__ x,
                                     u16* __restrict__ y, int64_t n, int H) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
        i < n; i += (int64_t)gridDim.x * blockDim.x)
-    stbf_(y + i, x[i] * ldbf_(s + i / H));
+    stbf(y + i, x[i] * ldbf(s + i / H));
 }
 
 // fused unit with two pre-activation gate inputs (xg_t + hg_t); hg is
@@ -58,17 +50,14 @@ __global__ void lstm_unit2_fwd_kernel(
     int64_t row = i / H;
     int hh = i % H;
     int64_t g0 = row * 4 * H + hh;
-    float gi = 1.f / (1.f + __expf(-(ldbf_(xg + g0) + hg[g0])));
-    float gf = 1.f / (1.f + __expf(-(ldbf_(xg + g0 + H) + hg[g0 + H])));
-    float go = 1.f / (1.f + __expf(-(ldbf_(xg + g0 + 2 * H) +
-                                     hg[g0 + 2 * H])));
-    float gg = tanhf(ldbf_(xg + g0 + 3 * H) + hg[g0 + 3 * H]);
-    float ct = ldbf_(cont + row);
-    float c = gf * c_prev[i] * ct + gi * gg;
-    c_out[i] = c;
-    stbf_(h_out + i, go * tanhf(c));
-    float* a = act + row * 4 * H + hh;
-    a[0] = gi; a[H] = gf; a[2 * H] = go; a[3 * H] = gg;
+    LstmCellFwd r = lstm_cell_fwd(
+        ldbf(xg + g0) + hg[g0], ldbf(xg + g0 + H) + hg[g0 + H],
+        ldbf(xg + g0 + 2 * H) + hg[g0 + 2 * H],
+        ldbf(xg + g0 + 3 * H) + hg[g0 + 3 * H], c_prev[i], ldbf(cont + row));
+    c_out[i] = r.c;
+    stbf(h_out + i, r.h);
+    float* a = act + g0;
+    a[0] = r.gi; a[H] = r.gf; a[2 * H] = r.go; a[3 * H] = r.gg;
   }
 }
 
@@ -83,22 +72,17 @@ __global__ void lstm_unit2_bwd_kernel(
     int64_t row = i / H;
     int hh = i % H;
     const float* a = act + row * 4 * H + hh;
-    float gi = a[0], gf = a[H], go = a[2 * H], gg = a[3 * H];
-    float tc = tanhf(c_out[i]);
-    float ct = ldbf_(cont + row);
-    float dhv = ldbf_(dy + i) +
-                (dh_rec != nullptr ? ldbf_(dh_rec + i) : 0.f);
-    float dc = dc_next[i] + dhv * go * (1.f - tc * tc);
-    float dov = dhv * tc;
-    float div = dc * gg;
-    float dgv = dc * gi;
-    float dfv = dc * c_prev[i] * ct;
-    dc_prev[i] = dc * gf * ct;
+    float dhv = ldbf(dy + i) +
+                (dh_rec != nullptr ? ldbf(dh_rec + i) : 0.f);
+    LstmCellBwd r = lstm_cell_bwd(
+        a[0], a[H], a[2 * H], a[3 * H], c_out[i], c_prev[i],
+        ldbf(cont + row), dhv, dc_next[i]);
+    dc_prev[i] = r.dc_prev;
     u16* dg = dgates + row * 4 * H + hh;
-    stbf_(dg, div * gi * (1.f - gi));
-    stbf_(dg + H, dfv * gf * (1.f - gf));
-    stbf_(dg + 2 * H, dov * go * (1.f - go));
-    stbf_(dg + 3 * H, dgv * (1.f - gg * gg));
+    stbf(dg, r.di);
+    stbf(dg + H, r.df);
+    stbf(dg + 2 * H, r.dO);
+    stbf(dg + 3 * H, r.dg);
   }
 }
 
@@ -121,8 +105,10 @@ void lstm_seq_fwd(const void* xg, const void* w_hc, const void* cont,
   // skinny [N,4H] recurrent GEMM
   int nb4h = (4 * H + 127) / 128;
   int sk = (448 + nb4h - 1) / nb4h;
-  COS_CHECK_HIP(hipMemsetAsync(h_in, 0, nh * 2, stream));  // h_-1 = 0
-  COS_CHECK_HIP(hipMemsetAsync(c, 0, nh * 4, stream));     // reused as c_-1? no
+  // h_-1 = c_-1 = 0: h_in[0] needs no cont scaling, and the zeroed c[0]
+  // is its own c_prev at t == 0 (each element is read before it is written)
+  COS_CHECK_HIP(hipMemsetAsync(h_in, 0, nh * 2, stream));
+  COS_CHECK_HIP(hipMemsetAsync(c, 0, nh * 4, stream));
   for (int t = 0; t < T; ++t) {
     const u16* cont_t = (const u16*)cont + (int64_t)t * N;
     const u16* xg_t = (const u16*)xg + (int64_t)t * N * 4 * H;
@@ -130,24 +116,16 @@ void lstm_seq_fwd(const void* xg, const void* w_hc, const void* cont,
     u16* h_in_t = (u16*)h_in + t * nh;
     float* c_t = c + t * nh;
     float* act_t = act + (int64_t)t * N * 4 * H;
-    if (t > 0) {
+    if (t > 0)
       rowscale_kernel<<<nb_(nh), 256, 0, stream>>>(
           (const u16*)h + (int64_t)(t - 1) * nh, cont_t, h_in_t, nh, H);
-    } else {
-      // h_in_0 already zero
-      rowscale_kernel<<<nb_(nh), 256, 0, stream>>>(
-          h_in_t, cont_t, h_in_t, nh, H);
-    }
     COS_CHECK_HIP(hipMemsetAsync(hg, 0, (int64_t)N * 4 * H * 4, stream));
     gemm_bf16(h_in_t, w_hc, hg, nullptr, N, 4 * H, H, H, H, 4 * H,
               false, false, 2, sk, false, 1.0f, N + 128, n_alloc_whc,
               stream);
-    const float* c_prev = (t > 0) ? c + (int64_t)(t - 1) * nh : nullptr;
-    // t==0: c_prev unused since cont_0 should be 0; still need a valid
-    // pointer — use c_t (will read garbage * cont ... safer: zero buffer)
+    const float* c_prev = (t > 0) ? c + (int64_t)(t - 1) * nh : c_t;
     lstm_unit2_fwd_kernel<<<nb_(nh), 256, 0, stream>>>(
-        (t > 0) ? c_prev : c_t /* zeroed above */, xg_t, hg,
-        cont_t, c_t, h_t, act_t, nh, H);
+        c_prev, xg_t, hg, cont_t, c_t, h_t, act_t, nh, H);
   }
 }
 
@@ -165,8 +143,8 @@ void lstm_seq_bwd(const void* dy, const void* w_hcT, const void* cont,
   COS_CHECK_HIP(hipMemsetAsync(dc_a, 0, nh * 4, stream));
   float* dc_next = dc_a;
   float* dc_prev = dc_b;
-  // zero buffer for c_prev at t=0 (cont_0 gates it off; values unused
-  // when cont==0, but must be finite): reuse dc_b after it's zeroed
+  // at t == 0 the zeroed dc_prev buffer doubles as the zero c_prev (each
+  // element is read before it is written)
   for (int t = T - 1; t >= 0; --t) {
     const u16* cont_t = (const u16*)cont + (int64_t)t * N;
     const u16* dy_t = (const u16*)dy + t * nh;

@@ -3,7 +3,8 @@
 //   pre[g][n][j] = b[gH+j] + sum over segments  a_seg[n][:] . W_seg[gH+j][:]
 //   segments: (x, W_xc [4H,D]), (cont_n * h_prev, W_hc [4H,H]),
 //             (x_static, W_xsc [4H,Ds]);  gates g = i,f,o,g
-//   c = cont*f*c_prev + i*g (fp32),  h = o*tanh(c) (bf16)
+//   c = cont*f*c_prev + i*g (fp32),  h = o*tanh(c) (bf16): lstm_cell.h's
+//   forward cell, the one every LSTM route applies
 //
 // At this M the op is pure weight streaming (LRCN: 16-24 MB of bf16 per
 // layer per token), so the weights go straight from memory to registers in
@@ -17,6 +18,7 @@
 // No MFMA, no atomics, no grid barrier: every (n, j) is written by one wave.
 
 #include "common.h"
+#include "lstm_cell.h"
 
 #include <stdexcept>
 #include <string>
@@ -158,18 +160,13 @@ __global__ __launch_bounds__(kStepThreads) void lstm_step_kernel(StepArgs p) {
   if (lane < p.N) {
     const int n = lane;
     const unsigned short* b = p.bias;
-    float xi = pre[0] + bf_lo(b[j]);
-    float xf = pre[1] + bf_lo(b[p.H + j]);
-    float xo = pre[2] + bf_lo(b[2 * p.H + j]);
-    float xg = pre[3] + bf_lo(b[3 * p.H + j]);
-    float gi = 1.f / (1.f + __expf(-xi));
-    float gf = 1.f / (1.f + __expf(-xf));
-    float go = 1.f / (1.f + __expf(-xo));
-    float gg = tanhf(xg);
     size_t o = (size_t)n * p.H + j;
-    float c = gf * p.c_prev[o] * p.cont[n] + gi * gg;
-    p.c_out[o] = c;
-    p.h_out[o] = (unsigned short)f2bf_bits(go * tanhf(c));
+    LstmCellFwd r = lstm_cell_fwd(
+        pre[0] + bf_lo(b[j]), pre[1] + bf_lo(b[p.H + j]),
+        pre[2] + bf_lo(b[2 * p.H + j]), pre[3] + bf_lo(b[3 * p.H + j]),
+        p.c_prev[o], p.cont[n]);
+    p.c_out[o] = r.c;
+    p.h_out[o] = (unsigned short)f2bf_bits(r.h);
   }
 }
 

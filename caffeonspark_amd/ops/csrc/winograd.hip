@@ -23,16 +23,7 @@
 
 namespace cosamd {
 
-typedef unsigned short u16;
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float ldbf(const u16* p) {
-  return bf2f(*reinterpret_cast<const bf16*>(p));
-}
-__device__ __forceinline__ void stbf(u16* p, float v) {
-  bf16 b = f2bf(v);
-  *p = *reinterpret_cast<u16*>(&b);
-}
 
 void gemm_bf16_batched(const void* A_, const void* B_, void* C,
                        const float* bias, int M, int N, int K, int lda,

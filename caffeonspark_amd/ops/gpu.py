@@ -2105,8 +2105,7 @@ def lstm_seq_forward(xg, w_hc, cont, ctx=None):
     dev_ = xg.device
     xg = _as_bf16(xg).contiguous()
     cont_b = _as_bf16(cont).contiguous()
-    whc = torch.zeros((_pad128(H4), H), dtype=torch.bfloat16, device=dev_)
-    whc[:H4] = _as_bf16(w_hc)
+    w_hc = _as_bf16(w_hc).contiguous()
     h = torch.empty((T, N, H), dtype=torch.bfloat16, device=dev_)
     c = torch.empty((T, N, H), dtype=torch.float32, device=dev_)
     act = torch.empty((T, N, H4), dtype=torch.float32, device=dev_)
@@ -2114,21 +2113,23 @@ def lstm_seq_forward(xg, w_hc, cont, ctx=None):
     h_in_store = torch.empty(((T * N + 128) * H,), dtype=torch.bfloat16,
                              device=dev_)
     h_in = h_in_store[:T * N * H].view(T, N, H)
-    hg = torch.empty((N, H4), dtype=torch.float32, device=dev_)
     if _lstm_persist_ok(N):
         # persistent whole-sequence kernel: recurrent weights stationary
         # in registers, grid-resident with in-kernel barriers (falls back
         # to the per-step loop when the watchdog reports non-residency)
         bar = torch.zeros(260, dtype=torch.int32, device=dev_)
-        rc = _ext.lstm_persist_fwd(xg, whc[:H4].contiguous() if not
-                                   whc[:H4].is_contiguous() else whc[:H4],
-                                   cont_b, h, c, act, h_in, hg, T, N, H,
-                                   bar)
+        rc = _ext.lstm_persist_fwd(xg, w_hc, cont_b, h, c, act, h_in,
+                                   T, N, H, bar)
         if rc == 0:
             _persist_track(bar)
             if ctx is not None:
                 ctx["route"] = "persist"
             return h, (cont_b, h, c, act, h_in, T, N, H)
+    # loop route: its GEMM wants the weight rows padded to the tile, and
+    # hg [N,4H] fp32 as the split-K target of each step
+    whc = torch.zeros((_pad128(H4), H), dtype=torch.bfloat16, device=dev_)
+    whc[:H4] = w_hc
+    hg = torch.empty((N, H4), dtype=torch.float32, device=dev_)
     _ext.lstm_seq_fwd(xg, whc[:H4], cont_b, h, c, act, h_in, hg,
                       T, N, H, whc.shape[0])
     if ctx is not None:
@@ -2195,21 +2196,21 @@ def lstm_seq_backward(dy, w_hc, cache, ctx=None):
     dxg_store = torch.empty(((T * N + 128) * H4,), dtype=torch.bfloat16,
                             device=dev_)
     dxg = dxg_store[:T * N * H4].view(T, N, H4)
-    dh_rec = torch.empty((N, H), dtype=torch.bfloat16, device=dev_)
-    dh_f = torch.empty((N, H), dtype=torch.float32, device=dev_)
-    dc_a = torch.empty((N, H), dtype=torch.float32, device=dev_)
-    dc_b = torch.empty((N, H), dtype=torch.float32, device=dev_)
     done = False
     if _lstm_persist_ok(N):
         bar = torch.zeros(260, dtype=torch.int32, device=dev_)
-        rc = _ext.lstm_persist_bwd(dy, whcT[:H].contiguous() if not
-                                   whcT[:H].is_contiguous() else whcT[:H],
-                                   cont_b, h, c, act, dxg, dh_f, dc_a,
-                                   dc_b, T, N, H, bar)
+        rc = _ext.lstm_persist_bwd(dy, whcT, cont_b, h, c, act, dxg,
+                                   T, N, H, bar)
         done = (rc == 0)
         if done:
             _persist_track(bar)
     if not done:
+        # loop-route scratch: recurrent dh (bf16 and its fp32 split-K
+        # target) and the two ping-pong dc buffers
+        dh_rec = torch.empty((N, H), dtype=torch.bfloat16, device=dev_)
+        dh_f, dc_a, dc_b = (
+            torch.empty((N, H), dtype=torch.float32, device=dev_)
+            for _ in range(3))
         _ext.lstm_seq_bwd(dy, whcT, cont_b, h, c, act, dxg, dh_rec, dh_f,
                           dc_a, dc_b, T, N, H, _pad128(H4))
     if ctx is not None:
